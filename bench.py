@@ -18,10 +18,18 @@ Workloads (BASELINE.json configs):
                         interpolation; the reference has no Conv2d / fp16 / learned weights).
 
 Prints ONE JSON line on rank 0 with the driver's fields plus ``roofline`` (HBM; algorithmic bytes
-per launch / HIP-event launch time) and, at N=1, ``cpu_baseline`` (CPU ports of the reference's algorithm --
-the loop-style ce_rule_baseline form and the tensorized form -- timed on the host cores on bounded samples of the same
-workload) and ``secondary`` (the other parity-pinned workloads, a few launches each, followed by the two extensions
-without a reference counterpart, each marked ``"parity": "unpinned extension"``).
+per launch / HIP-event launch time of the timed steps).  A plain run does only what that line needs: set-up, warm-up,
+the timed steps, the outputs (``--dump-outputs``) and the line.  ``--full`` adds what takes measurements of its own: at
+N=1, ``cpu_baseline`` (CPU ports of the reference's algorithm -- the loop-style ce_rule_baseline form and the tensorized
+form -- timed on the host cores on bounded samples of the same workload) and ``secondary`` (the other parity-pinned
+workloads, a few launches each, followed by the two extensions without a reference counterpart, each marked
+``"parity": "unpinned extension"``); the denoiser's own MFMA roofline (``pusch273_4rx_denoise``); a sanity check of the
+outputs.
+
+``--dump-outputs DIR`` writes what the last timed step returned (rank 0) as ``DIR/<name>.npy``: the five per-(slot, port)
+scalars in full (float64) and the channel estimates of a fixed, seeded sample of (slot, port) items (float32 re/im),
+at most 64 MB in all.  The synthetic inputs are generated from fixed seeds, so two builds run with the same arguments
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -247,6 +255,37 @@ def secondary_lines(E, S, plan, case, rx, pilots, out, n_slots, n_ports, dev, it
     return res
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ITEMS = 128            # 128 items x 3276 x 14 complex64 = 47 MB of channel estimates at 273 PRB
+DUMP_SEED = 5150
+
+
+def dump_outputs(out, dst, budget=DUMP_BUDGET_BYTES, max_items=DUMP_MAX_ITEMS):
+    """`out` = the six tensors `estimate_with_plan` returns.  Writes `noise`, `rsrp`, `epre`, `ta`, `cfo_hz` ([slots, ports]
+    float64, whole), `ch_est_sample` ([k, n_sc, n_sym, L, 2] float32, re/im) = the estimates of k (slot, port) items drawn
+    with a fixed seed, and `ch_est_sample_items` ([k, 2] float64: slot, port of each).  Returns {name: array}."""
+    import numpy as np
+    import torch
+
+    dst = Path(dst)
+    dst.mkdir(parents=True, exist_ok=True)
+    ch = out[0]
+    B, R = ch.shape[:2]
+    n = B * R
+    arrays = {name: t.reshape(B, R).cpu().numpy().astype(np.float64)
+              for name, t in zip(("noise", "rsrp", "epre", "ta", "cfo_hz"), out[1:])}
+    left = budget - sum(a.nbytes for a in arrays.values())
+    per_item = ch[0, 0].numel() * 8 + 16                                # complex64 estimate + its (slot, port) pair
+    k = max(0, min(n, max_items, left // per_item))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    sel = ch.reshape(n, *ch.shape[2:]).index_select(0, torch.as_tensor(idx, device=ch.device))
+    arrays["ch_est_sample"] = torch.view_as_real(sel).cpu().numpy()
+    arrays["ch_est_sample_items"] = np.stack([idx // R, idx % R], axis=1).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(dst / f"{name}.npy", a)
+    return arrays
+
+
 def _with_smoothing(cfg, smoothing):
     import copy
 
@@ -263,8 +302,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="pusch273_4rx_filter", choices=sorted(WORKLOADS))
     ap.add_argument("--slots", type=int, default=None, help="slots per GPU (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads timed after the headline (N=1)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and the secondary workloads (N=1), the denoiser's own "
+                                                         "roofline and the output sanity check (off: only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads timed after the headline (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -281,7 +324,7 @@ def main():
     case = S.bench_case(wl["smoothing"], 1, seed=1234 + rank)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(case, n_ports, interp=wl.get("interp", "linear"), denoise=bool(wl.get("denoise")))   # before any GPU initialisation (forks)
 
     import torch
@@ -331,13 +374,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    setup_s = time.perf_counter() - t_start      # imports, process group, plan, synthetic inputs resident, first launch (+ the CPU baseline at N = 1)
+    setup_s = time.perf_counter() - t_start      # imports, process group, plan, synthetic inputs resident, first launch (+ the CPU baseline with --full at N = 1)
     elapsed, kernel_ms = time_steps(step, barrier, args.steps, args.warmup,
                                     lambda: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
     elapsed, kernel_ms = max_over_ranks([elapsed, kernel_ms], "cpu" if rehearse else dev)  # measurement only, not data path
+    if args.dump_outputs and rank == 0:          # before anything below launches into `out` again
+        dump_outputs(out, args.dump_outputs)
 
-    # sanity: the batch really was estimated (finite outputs, CFO in the generated range)
-    assert bool(torch.isfinite(out[1]).all()) and bool(torch.isfinite(out[0][-1, -1].real).all())
+    if args.full:
+        # sanity: the batch really was estimated (finite outputs, CFO in the generated range)
+        assert bool(torch.isfinite(out[1]).all()) and bool(torch.isfinite(out[0][-1, -1].real).all())
 
     bytes_per_slot = n_ports * plan.alg_bytes_per_item + plan.pilot_bytes_per_slot
     bytes_per_launch = n_slots * bytes_per_slot
@@ -372,9 +418,13 @@ def main():
                      "kernel": "ce_estimate_kernel<1,1,2,7,%d>" % (1 if wl["smoothing"] == "filter" else 3 if wl["smoothing"] == "mmse" else 0), "kernel_ms": kernel_ms,
                      "alg_bytes_per_slot": bytes_per_slot, "alg_bytes_per_launch": bytes_per_launch},
     }
-    if world == 1 and args.workload == "pusch273_4rx_filter" and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "pusch273_4rx_filter" and not args.no_secondary:
         line["secondary"] = secondary_lines(E, S, plan, case, rx, pilots, out, n_slots, n_ports, dev)
-    if denoiser is not None:
+    if denoiser is not None and not args.full:
+        # the HBM roofline above would charge the estimation's bytes to both kernels' time; the denoiser's own takes a
+        # timed run of its own (--full)
+        line["roofline"] = None
+    elif denoiser is not None:
         # dominant kernel of this workload: the denoiser; timed on its own (same stream, same resident batch)
         d0, d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         d0.record()
@@ -389,6 +439,7 @@ def main():
                             "traffic": None, "kernel": "ce_denoise_kernel", "kernel_ms": dn_ms, "alg_flop_per_launch": flops,
                             "note": "useful flops of the three 3x3 layers (2->16->16->2); the kernel issues 1.8x that on MFMA (K padding of layer 1, banded layer 3)",
                             "estimation_kernel_ms": kernel_ms - dn_ms}
+    if denoiser is not None:
         line["dtype"] = "f32 estimation + f16 Conv2d (f32 accumulate)"
         line["config"]["extension"] = "Conv2d denoiser, random weights, parity unpinned"
     if cpu is not None:

@@ -13,7 +13,7 @@ B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
 SQ="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"
 if [ "$WHAT" != geo ]; then
 hipcc --offload-arch=gfx950 -O3 -o /tmp/rwmix tools/micro/rwmix.hip 2>/dev/null && /tmp/rwmix > $O/${P}_rwmix.log 2>&1
-python3 bench.py > $O/${P}_bench_same_lease.log 2> $O/${P}_bench_same_lease.err || exit 1
+python3 bench.py --full > $O/${P}_bench_same_lease.log 2> $O/${P}_bench_same_lease.err || exit 1
 rocprofv3 --kernel-trace --stats --kernel-include-regex "ce_estimate|ce_narrow" --output-format csv -d $O/${P}_bench_trace -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/${P}_bench_trace.log 2>&1 || exit 1
 rocprofv3 --kernel-include-regex "ce_estimate|ce_narrow" --pmc FETCH_SIZE --output-format csv -d $O/${P}_bench_fetch -- $B > $O/${P}_bench_fetch.log 2>&1 || exit 1
 rocprofv3 --kernel-include-regex "ce_estimate|ce_narrow" --pmc WRITE_SIZE --output-format csv -d $O/${P}_bench_write -- $B > $O/${P}_bench_write.log 2>&1 || exit 1
