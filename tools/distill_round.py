@@ -26,7 +26,7 @@ with open(f"{OUT}/{tag}_kernel_stats.csv", "w") as f:
     for r in ks[:12]:
         r = dict(r); r["Name"] = r["Name"][:160]; w.writerow(r.values())
 ce = [r for r in ks if "ce_estimate" in r["Name"]][0]
-out = {"lease": "one gpurun call: bench.py, tools/micro/rwmix.hip, rocprofv3 trace and PMC passes back to back on the same box",
+out = {"lease": "one lease (tools/gpu_profile_round.sh): bench.py, tools/micro/rwmix.hip, rocprofv3 trace and PMC passes back to back on the same box",
        "command": "rocprofv3 --kernel-trace --stats --kernel-include-regex ce_estimate --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary",
        "kernel": ce["Name"][:90], "calls": int(ce["Calls"]), "avg_ns": float(ce["AverageNs"]), "min_ns": int(ce["MinNs"]), "max_ns": int(ce["MaxNs"])}
 
