@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CE_ABI_VERSION 2
+#define CE_ABI_VERSION 3
 
 #define CE_MAX_LAYERS 4   /* Tx layers (pilots.shape[2]); 2 per CDM group (T:551-552) */
 #define CE_MAX_CDM 2
@@ -108,7 +108,21 @@ typedef struct ce_plan_host_view {
   double two_pi_nsamples[CE_MAX_HOPS];            /* 2*pi*nSamples (T:418-426) */
   double n_pilots, noise_den;                     /* T:901-915 */
   float mmse_w[2][CE_MMSE_BLOCK][CE_MMSE_BLOCK];  /* CE_SMOOTH_MMSE: Re / Im of W[m][k] */
+  /* the kernel selection (ce_api.hip: select_kernel) -- which compiled instance and which of its run-time branches a launch takes */
+  int32_t reg_kpt;      /* pilot REs per thread of the band tier: 1 / 2 / 4 / 7 (meaningful where reg_nd > 0) */
+  int32_t feat;         /* feature set the kernel carries: 0 none / mean, 1 + RC filter, 3 + extensions (mmse, iterated in-painting) */
+  int32_t ta_lp;        /* 2: two time-alignment transforms side by side (layers of a hop, or the two hops of one layer), else 1 */
+  int32_t ta_over_p;    /* 1: the last hop's second set of TA residue blocks is laid over the first hop's P */
+  int32_t pil_stash;    /* 0, or (LDS offset in 8-byte units) | (DM-RS symbols of the hop parked in the LDS << 24) */
+  int32_t sym_overlap;  /* 1: the two hops' fill rectangles share OFDM symbols (element-wise writer) */
+  int32_t cnn_comb2;    /* interp "cnn": 1 comb-2 closed form, 2 binomial closed form, 0 iterated in-painting */
+  int32_t kernel_unit;  /* CE_UNIT_*: the instantiation unit the launch is routed to */
+  int32_t kernel_key;   /* the key the unit's switch selects the instance by: CE_KERNEL_KEY, or layers * 10 + hops (CE_UNIT_NARROW) */
 } ce_plan_host_view;
+
+/* Instantiation units of the estimation kernels (csrc/ce_inst_*.hip), as reported in ce_plan_host_view.kernel_unit. */
+enum { CE_UNIT_NARROW = 0, CE_UNIT_REG_H1_F0 = 1, CE_UNIT_REG_H1_F1 = 2, CE_UNIT_REG_H1_F1W = 3, CE_UNIT_REG_H2_F0 = 4,
+       CE_UNIT_REG_H2_F1 = 5, CE_UNIT_GEN_H1 = 6, CE_UNIT_GEN_H2 = 7 };
 
 /* Same validation and float64 derivation as ce_plan_create but touches no GPU: usable on a CPU-only host. */
 int ce_plan_derive_host(const ce_plan_desc* desc, ce_plan_host_view* view);

@@ -25,7 +25,7 @@ SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 
-CE_ABI_VERSION = 2
+CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
 SMOOTHING = {"none": 0, "mean": 1, "filter": 2, "mmse": 3}   # "mmse": extension, not in the reference
 INTERP = {"linear": 0, "cnn": 1}
@@ -62,7 +62,15 @@ class PlanHostView(C.Structure):
                 ("r_ord", ((C.c_int32 * 12) * CE_MAX_CDM) * CE_MAX_HOPS),
                 ("alpha", ((C.c_float * 12) * CE_MAX_CDM) * CE_MAX_HOPS),
                 ("rc", C.c_double * 31), ("sst", C.c_double * CE_MAX_SYMBOLS), ("two_pi_nsamples", C.c_double * CE_MAX_HOPS),
-                ("n_pilots", C.c_double), ("noise_den", C.c_double), ("mmse_w", ((C.c_float * 32) * 32) * 2)]
+                ("n_pilots", C.c_double), ("noise_den", C.c_double), ("mmse_w", ((C.c_float * 32) * 32) * 2),
+                ("reg_kpt", C.c_int32), ("feat", C.c_int32), ("ta_lp", C.c_int32), ("ta_over_p", C.c_int32),
+                ("pil_stash", C.c_int32), ("sym_overlap", C.c_int32), ("cnn_comb2", C.c_int32),
+                ("kernel_unit", C.c_int32), ("kernel_key", C.c_int32)]
+
+
+# PlanHostView.kernel_unit (CE_UNIT_* of include/ce_hip.h) -> the instantiation unit's source
+KERNEL_UNITS = ["ce_inst_narrow.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip",
+                "ce_inst_reg_h2_f0.hip", "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip"]
 
 
 EXPORTS = ["ce_plan_create", "ce_plan_destroy", "ce_plan_get_info", "ce_plan_derive_host", "ce_estimate_batch",

@@ -608,14 +608,29 @@ int derive_plan(const ce_plan_desc* d, const CeKnobs& knobs, HostPlan& hp) {
 
 }  // namespace
 
-// Routes a launch / prepare to the translation unit holding the plan's instantiation (ce_inst_*.hip).
-static int kernel_op(int op, const CeDevPlan& P, const CeLaunchCtx& c) {
-  if (P.narrow) return ce_tu_narrow(op, P.n_layers * 10 + P.n_hops, c);
-  const int key = CE_KERNEL_KEY(P.feat, P.n_layers, P.reg_nd, P.reg_kpt);
+// The translation unit (CE_UNIT_*) holding the plan's instantiation (ce_inst_*.hip) and the key its switch selects it by.
+static int kernel_route(const CeDevPlan& P, int* key) {
+  if (P.narrow) { *key = P.n_layers * 10 + P.n_hops; return CE_UNIT_NARROW; }
+  *key = CE_KERNEL_KEY(P.feat, P.n_layers, P.reg_nd, P.reg_kpt);
   const bool two = P.n_hops == 2;
-  if (P.reg_nd == 0 || P.feat == 3) return two ? ce_tu_gen_h2(op, key, c) : ce_tu_gen_h1(op, key, c);
-  if (P.feat == 0) return two ? ce_tu_reg_h2_f0(op, key, c) : ce_tu_reg_h1_f0(op, key, c);
-  return two ? ce_tu_reg_h2_f1(op, key, c) : P.reg_kpt >= 4 ? ce_tu_reg_h1_f1w(op, key, c) : ce_tu_reg_h1_f1(op, key, c);
+  if (P.reg_nd == 0 || P.feat == 3) return two ? CE_UNIT_GEN_H2 : CE_UNIT_GEN_H1;
+  if (P.feat == 0) return two ? CE_UNIT_REG_H2_F0 : CE_UNIT_REG_H1_F0;
+  return two ? CE_UNIT_REG_H2_F1 : P.reg_kpt >= 4 ? CE_UNIT_REG_H1_F1W : CE_UNIT_REG_H1_F1;
+}
+
+// Routes a launch / prepare to the plan's instantiation.
+static int kernel_op(int op, const CeDevPlan& P, const CeLaunchCtx& c) {
+  int key = 0;
+  switch (kernel_route(P, &key)) {
+    case CE_UNIT_NARROW: return ce_tu_narrow(op, key, c);
+    case CE_UNIT_REG_H1_F0: return ce_tu_reg_h1_f0(op, key, c);
+    case CE_UNIT_REG_H1_F1: return ce_tu_reg_h1_f1(op, key, c);
+    case CE_UNIT_REG_H1_F1W: return ce_tu_reg_h1_f1w(op, key, c);
+    case CE_UNIT_REG_H2_F0: return ce_tu_reg_h2_f0(op, key, c);
+    case CE_UNIT_REG_H2_F1: return ce_tu_reg_h2_f1(op, key, c);
+    case CE_UNIT_GEN_H1: return ce_tu_gen_h1(op, key, c);
+    default: return ce_tu_gen_h2(op, key, c);
+  }
 }
 
 #if defined(CE_STAMPS)
@@ -690,6 +705,9 @@ int ce_plan_derive_host(const ce_plan_desc* d, ce_plan_host_view* v) {
     memcpy(v->last_idx[h], H.last_idx, sizeof(v->last_idx[h])); memcpy(v->r_ord[h], H.r_ord, sizeof(v->r_ord[h])); memcpy(v->alpha[h], H.alpha, sizeof(v->alpha[h]));
   }
   if (!hp.mmse_w.empty()) memcpy(v->mmse_w, hp.mmse_w.data(), sizeof(v->mmse_w));
+  v->reg_kpt = P.reg_kpt; v->feat = P.feat; v->ta_lp = P.ta_lp; v->ta_over_p = P.ta_over_p; v->pil_stash = P.pil_stash;
+  v->sym_overlap = P.sym_overlap; v->cnn_comb2 = P.cnn_comb2;
+  v->kernel_unit = kernel_route(P, &v->kernel_key);
   return CE_OK;
 }
 
