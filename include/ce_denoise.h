@@ -9,11 +9,13 @@
  *
  * Operator, per (slot, port, layer) plane h[subcarrier][symbol] (complex64, 14 symbols):
  *     x0 = (Re h, Im h)                                            2 channels, rounded to fp16
- *     x1 = ReLU(conv3x3(x0, W1) + b1)                              16 channels, fp16
- *     x2 = ReLU(conv3x3(x1, W2) + b2)                              16 channels, fp16
+ *     x1 = sat(ReLU(conv3x3(x0, W1) + b1))                         16 channels, fp16
+ *     x2 = sat(ReLU(conv3x3(x1, W2) + b2))                         16 channels, fp16
  *     out = h + (conv3x3(x2, W3) + b3)                             residual, float32
  * conv3x3 = cross-correlation with zero padding ("same") over (subcarrier, symbol); fp16 operands, float32
- * accumulation on v_mfma_f32_16x16x32_f16.
+ * accumulation on v_mfma_f32_16x16x32_f16.  sat = min(., 65504), the largest finite fp16: an activation never
+ * becomes Inf, so an output depends on nothing outside its 3 x 3 x 3 receptive field (the kernel's zero-padded
+ * weight fragments would turn 0 x Inf into a NaN that reaches further).
  */
 #ifndef CE_DENOISE_H
 #define CE_DENOISE_H

@@ -3,15 +3,23 @@
 "Parity unpinned": the reference (pjookim/srsran-ce-pytorch) has no learned denoiser -- its `ce_dl_cnn.py` is a fixed
 3-tap in-painting -- so there is nothing upstream to check this against; this file is the only oracle of
 `ce_denoise_batch`.  It follows the operator definition in the header literally: fp16-rounded weights and
-activations, wide accumulation, zero padding at every layer, float32 residual."""
+activations (saturated at the fp16 maximum), wide accumulation, zero padding at every layer, float32 residual."""
 from __future__ import annotations
 
 import numpy as np
 
 
+FP16_MAX = 65504.0   # the largest finite fp16: where the activations saturate
+
+
 def _h(x: np.ndarray) -> np.ndarray:
-    """round to fp16 and back (what the kernel stores between layers)"""
+    """round to fp16 and back (the input and the weights as the kernel holds them)"""
     return np.asarray(x, np.float32).astype(np.float16).astype(np.float64)
+
+
+def _act(x: np.ndarray) -> np.ndarray:
+    """ReLU saturated at the fp16 maximum, rounded to fp16 (what the kernel stores between layers)"""
+    return _h(np.minimum(np.maximum(x, 0.0), FP16_MAX))
 
 
 def conv3x3(x: np.ndarray, w: np.ndarray, b: np.ndarray) -> np.ndarray:
@@ -29,8 +37,8 @@ def conv3x3(x: np.ndarray, w: np.ndarray, b: np.ndarray) -> np.ndarray:
 def denoise_plane(h: np.ndarray, w1, b1, w2, b2, w3, b3) -> np.ndarray:
     """h [n_sc, 14] complex64 -> denoised complex64."""
     x0 = _h(np.stack([h.real, h.imag]))
-    x1 = _h(np.maximum(conv3x3(x0, _h(w1), b1), 0.0))
-    x2 = _h(np.maximum(conv3x3(x1, _h(w2), b2), 0.0))
+    x1 = _act(conv3x3(x0, _h(w1), b1))
+    x2 = _act(conv3x3(x1, _h(w2), b2))
     r = conv3x3(x2, _h(w3), b3)
     out = h.astype(np.complex64).copy()
     out.real += r[0].astype(np.float32)

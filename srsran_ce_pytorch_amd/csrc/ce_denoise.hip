@@ -72,8 +72,11 @@ __device__ __forceinline__ int tap_off(int tap) {  // pixel offset of tap t = 3 
 constexpr int ROW_BYTES16 = DN_COLS * DN_C * 2;  // one image row of a 16-channel layer: 512 B
 constexpr int ROW_BYTES0 = DN_COLS * 4;          // one image row of x0 (fp16 re, im): 64 B
 
-// fp16 + ReLU of one D fragment (c_out 4g .. 4g+3 of one pixel): round first, then a packed max -- rounding to
-// nearest is monotonic and keeps the sign, so this equals fp16(ReLU(x)); 2 converts + 2 packed max instead of 8 + 2
+// fp16 + ReLU of one D fragment (c_out 4g .. 4g+3 of one pixel): round first, then a packed max and a packed min --
+// rounding to nearest is monotonic and keeps the sign, so this equals fp16(min(ReLU(x), 65504)); 2 converts + 2 packed
+// max + 2 packed min instead of 8 + 2 + 2.  The saturation keeps every activation finite: the MFMAs below multiply
+// activations by weights that are zero by design (layer 1's K padding, layer 2's last C fragment, layer 3's banded
+// K-steps), and 0 x Inf = NaN would carry one overflowing activation out of the 3 x 3 x 3 receptive field.
 typedef _Float16 half2x __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 masked(float2 v, bool ok) {  // v, or +0 where !ok, without a branch
   const unsigned m = ok ? 0xFFFFFFFFu : 0u;
@@ -83,9 +86,9 @@ __device__ __forceinline__ float2 masked(float2 v, bool ok) {  // v, or +0 where
 // an exec-masked store (s_and_saveexec + branch + restore around every tile's ds_write)
 __device__ __forceinline__ half4 relu_h4(f32x4 acc, unsigned keep) {
   half2x lo = half2x{(_Float16)acc[0], (_Float16)acc[1]}, hi = half2x{(_Float16)acc[2], (_Float16)acc[3]};
-  const half2x z = half2x{0, 0};
-  lo = __builtin_elementwise_max(lo, z);
-  hi = __builtin_elementwise_max(hi, z);
+  const half2x z = half2x{0, 0}, top = half2x{65504, 65504};   // the largest finite fp16
+  lo = __builtin_elementwise_min(__builtin_elementwise_max(lo, z), top);
+  hi = __builtin_elementwise_min(__builtin_elementwise_max(hi, z), top);
   unsigned ulo, uhi;
   __builtin_memcpy(&ulo, &lo, 4);
   __builtin_memcpy(&uhi, &hi, 4);
@@ -250,8 +253,10 @@ __global__ __launch_bounds__(DN_NT, DN_MIN_WAVES) void ce_denoise_kernel(float2*
         }
         asm volatile("" ::: "memory");
         half8 b;
+        // taps >= 9 (K padding) have zero weights; their lanes read tap 4, the output's own pixel (rd0), so 0 x a
+        // non-finite input stays inside that output's receptive field
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {  // taps >= 9 (K padding) have zero weights: whatever finite pixel their lanes read does not matter
+        for (int q = 0; q < 4; ++q) {
           b[2 * q] = px[k & 1][q][0];
           b[2 * q + 1] = px[k & 1][q][1];
         }
