@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 
@@ -76,6 +76,34 @@ KERNEL_UNITS = ["ce_inst_narrow.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f
 EXPORTS = ["ce_plan_create", "ce_plan_destroy", "ce_plan_get_info", "ce_plan_derive_host", "ce_estimate_batch",
            "ce_estimate_batch_stages", "ce_time_batch", "ce_last_error", "ce_abi_version"]
 EXPORTS_DENOISE = ["ce_denoiser_create", "ce_denoiser_destroy", "ce_denoise_batch"]   # include/ce_denoise.h (extension)
+EXPORTS_DMRS = ["ce_dmrs_derive_host", "ce_dmrs_plan_create", "ce_dmrs_plan_destroy", "ce_dmrs_plan_get_info",
+                "ce_dmrs_generate"]                                                       # include/ce_dmrs.h (extension)
+CE_DMRS_MAX_WORDS, CE_DMRS_MAX_RE = 136, 2048
+
+
+class DmrsHopDesc(C.Structure):
+    _fields_ = [("dmrs_symbols", C.c_uint8 * CE_MAX_SYMBOLS), ("re_mask", C.c_uint16 * CE_MAX_CDM),
+                ("mask_prbs", C.POINTER(C.c_uint8))]
+
+
+class DmrsDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("n_prb_grid", C.c_int32), ("grid_start_crb", C.c_int32),
+                ("n_sym", C.c_int32), ("n_symb_slot", C.c_int32), ("n_layers", C.c_int32), ("n_hops", C.c_int32),
+                ("hop", DmrsHopDesc * CE_MAX_HOPS)]
+
+
+class DmrsInfo(C.Structure):
+    _fields_ = [("n_re", C.c_int32), ("n_dmrs_total", C.c_int32), ("bytes_per_slot", C.c_int64)]
+
+
+class DmrsHostView(C.Structure):
+    _fields_ = [("n_re", C.c_int32), ("n_dmrs_total", C.c_int32), ("ppp", C.c_int32), ("reserved0", C.c_int32),
+                ("col_hop", C.c_int32 * CE_MAX_SYMBOLS), ("col_sym", C.c_int32 * CE_MAX_SYMBOLS),
+                ("word0", C.c_int32 * CE_MAX_HOPS), ("n_words", C.c_int32 * CE_MAX_HOPS),
+                ("x1", (C.c_uint32 * CE_DMRS_MAX_WORDS) * CE_MAX_HOPS),
+                ("t", ((C.c_uint32 * CE_DMRS_MAX_WORDS) * 31) * CE_MAX_HOPS),
+                ("m", (C.c_int32 * CE_DMRS_MAX_RE) * CE_MAX_HOPS),
+                ("odd_sign", (C.c_uint8 * CE_DMRS_MAX_RE) * CE_MAX_HOPS)]
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -104,7 +132,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -186,6 +214,16 @@ def load() -> C.CDLL:
     lib.ce_denoiser_destroy.restype = None
     lib.ce_denoise_batch.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp]
     lib.ce_denoise_batch.restype = C.c_int
+    lib.ce_dmrs_derive_host.argtypes = [C.POINTER(DmrsDesc), C.POINTER(DmrsHostView)]
+    lib.ce_dmrs_derive_host.restype = C.c_int
+    lib.ce_dmrs_plan_create.argtypes = [C.POINTER(DmrsDesc), C.POINTER(vp)]
+    lib.ce_dmrs_plan_create.restype = C.c_int
+    lib.ce_dmrs_plan_destroy.argtypes = [vp]
+    lib.ce_dmrs_plan_destroy.restype = None
+    lib.ce_dmrs_plan_get_info.argtypes = [vp, C.POINTER(DmrsInfo)]
+    lib.ce_dmrs_plan_get_info.restype = C.c_int
+    lib.ce_dmrs_generate.argtypes = [vp, vp, vp, vp, i64p, C.c_int64, vp, vp]
+    lib.ce_dmrs_generate.restype = C.c_int
     if lib.ce_abi_version() != CE_ABI_VERSION:
         raise RuntimeError(f"libce_hip.so ABI {lib.ce_abi_version()} != binding {CE_ABI_VERSION}; rebuild")
     _lib = lib
