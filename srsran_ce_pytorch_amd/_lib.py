@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 
@@ -106,6 +106,31 @@ class DmrsHostView(C.Structure):
                 ("odd_sign", (C.c_uint8 * CE_DMRS_MAX_RE) * CE_MAX_HOPS)]
 
 
+EXPORTS_EQ = ["ce_eq_derive_host", "ce_eq_plan_create", "ce_eq_plan_destroy", "ce_eq_plan_get_info",
+              "ce_eq_equalize"]                                                           # include/ce_eq.h (extension)
+CE_EQ_MAX_PORTS, CE_EQ_CHUNK_SC = 8, 36
+
+
+class EqHopDesc(C.Structure):
+    _fields_ = [("dmrs_symbols", C.c_uint8 * CE_MAX_SYMBOLS), ("reserved_re_mask", C.c_uint16), ("prb_start", C.c_int32),
+                ("n_prbs", C.c_int32), ("start_symbol", C.c_int32), ("n_alloc_symbols", C.c_int32)]
+
+
+class EqDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("n_prb_grid", C.c_int32), ("n_sym", C.c_int32),
+                ("n_layers", C.c_int32), ("n_hops", C.c_int32), ("hop", EqHopDesc * CE_MAX_HOPS)]
+
+
+class EqInfo(C.Structure):
+    _fields_ = [("n_data_re", C.c_int32), ("reserved0", C.c_int32), ("bytes_per_slot", C.c_int64)]
+
+
+class EqHostView(C.Structure):
+    _fields_ = [("sym_hop", C.c_int32 * CE_MAX_SYMBOLS), ("data_mask", C.c_int32 * CE_MAX_SYMBOLS),
+                ("data_res_per_prb", C.c_int32 * CE_MAX_SYMBOLS), ("first_row", C.c_int32 * CE_MAX_SYMBOLS),
+                ("n_data_re", C.c_int32)]
+
+
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
 # VGPRs (the default AGPR form costs four v_accvgpr_read per 16x16 tile in a kernel bound by vector-instruction issue)
 EXTRA_FLAGS = {"ce_denoise.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
@@ -132,7 +157,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", INCLUDE / "ce_eq.h", Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -224,6 +249,16 @@ def load() -> C.CDLL:
     lib.ce_dmrs_plan_get_info.restype = C.c_int
     lib.ce_dmrs_generate.argtypes = [vp, vp, vp, vp, i64p, C.c_int64, vp, vp]
     lib.ce_dmrs_generate.restype = C.c_int
+    lib.ce_eq_derive_host.argtypes = [C.POINTER(EqDesc), C.POINTER(EqHostView)]
+    lib.ce_eq_derive_host.restype = C.c_int
+    lib.ce_eq_plan_create.argtypes = [C.POINTER(EqDesc), C.POINTER(vp)]
+    lib.ce_eq_plan_create.restype = C.c_int
+    lib.ce_eq_plan_destroy.argtypes = [vp]
+    lib.ce_eq_plan_destroy.restype = None
+    lib.ce_eq_plan_get_info.argtypes = [vp, C.POINTER(EqInfo)]
+    lib.ce_eq_plan_get_info.restype = C.c_int
+    lib.ce_eq_equalize.argtypes = [vp, vp, i64p, vp, vp, C.c_int64, C.c_int32, vp, vp, vp]
+    lib.ce_eq_equalize.restype = C.c_int
     if lib.ce_abi_version() != CE_ABI_VERSION:
         raise RuntimeError(f"libce_hip.so ABI {lib.ce_abi_version()} != binding {CE_ABI_VERSION}; rebuild")
     _lib = lib
