@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 
@@ -131,6 +131,26 @@ class EqHostView(C.Structure):
                 ("n_data_re", C.c_int32)]
 
 
+EXPORTS_DEMOD = ["ce_demod_derive_host", "ce_demod_copy_tables", "ce_demod_plan_create", "ce_demod_plan_destroy",
+                 "ce_demod_plan_get_info", "ce_demod_demap"]                              # include/ce_demod.h (extension)
+CE_DEMOD_MAX_BITS, CE_DEMOD_BLOCK_WORDS, CE_DEMOD_TILE_SYMBOLS = 1 << 21, 8, 1024
+CE_DEMOD_OUT_F32, CE_DEMOD_OUT_I8 = 0, 1
+
+
+class DemodDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("qm", C.c_int32), ("out_format", C.c_int32),
+                ("descramble", C.c_int32), ("n_symbols", C.c_int32), ("llr_scale", C.c_float)]
+
+
+class DemodInfo(C.Structure):
+    _fields_ = [("n_bits", C.c_int32), ("out_elem_bytes", C.c_int32), ("bytes_per_slot", C.c_int64)]
+
+
+class DemodHostView(C.Structure):
+    _fields_ = [("n_bits", C.c_int32), ("n_words", C.c_int32), ("block_words", C.c_int32), ("n_blocks", C.c_int32),
+                ("tile_symbols", C.c_int32), ("n_tiles", C.c_int32), ("table_bytes", C.c_int64)]
+
+
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
 # VGPRs (the default AGPR form costs four v_accvgpr_read per 16x16 tile in a kernel bound by vector-instruction issue)
 EXTRA_FLAGS = {"ce_denoise.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
@@ -157,7 +177,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", INCLUDE / "ce_eq.h", Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", INCLUDE / "ce_eq.h", INCLUDE / "ce_demod.h", Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -259,6 +279,18 @@ def load() -> C.CDLL:
     lib.ce_eq_plan_get_info.restype = C.c_int
     lib.ce_eq_equalize.argtypes = [vp, vp, i64p, vp, vp, C.c_int64, C.c_int32, vp, vp, vp]
     lib.ce_eq_equalize.restype = C.c_int
+    lib.ce_demod_derive_host.argtypes = [C.POINTER(DemodDesc), C.POINTER(DemodHostView)]
+    lib.ce_demod_derive_host.restype = C.c_int
+    lib.ce_demod_copy_tables.argtypes = [C.POINTER(DemodDesc), vp, vp]
+    lib.ce_demod_copy_tables.restype = C.c_int
+    lib.ce_demod_plan_create.argtypes = [C.POINTER(DemodDesc), C.POINTER(vp)]
+    lib.ce_demod_plan_create.restype = C.c_int
+    lib.ce_demod_plan_destroy.argtypes = [vp]
+    lib.ce_demod_plan_destroy.restype = None
+    lib.ce_demod_plan_get_info.argtypes = [vp, C.POINTER(DemodInfo)]
+    lib.ce_demod_plan_get_info.restype = C.c_int
+    lib.ce_demod_demap.argtypes = [vp, vp, vp, vp, vp, i64p, C.c_int64, vp, vp]
+    lib.ce_demod_demap.restype = C.c_int
     if lib.ce_abi_version() != CE_ABI_VERSION:
         raise RuntimeError(f"libce_hip.so ABI {lib.ce_abi_version()} != binding {CE_ABI_VERSION}; rebuild")
     _lib = lib
