@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 
@@ -151,6 +151,30 @@ class DemodHostView(C.Structure):
                 ("tile_symbols", C.c_int32), ("n_tiles", C.c_int32), ("table_bytes", C.c_int64)]
 
 
+EXPORTS_RM = ["ce_rm_derive_host", "ce_rm_plan_create", "ce_rm_plan_destroy", "ce_rm_plan_get_info",
+              "ce_rm_recover"]                                                            # include/ce_rm.h (extension)
+CE_RM_F32, CE_RM_I8, CE_RM_MAX_SLOT_ELEMS, CE_RM_TILE_UNITS = 0, 1, 1 << 24, 1024
+
+
+class RmDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("base_graph", C.c_int32), ("tbs", C.c_int32),
+                ("qm", C.c_int32), ("n_layers", C.c_int32), ("g_bits", C.c_int32), ("format", C.c_int32),
+                ("n_ref", C.c_int32), ("filler_llr", C.c_float)]
+
+
+class RmInfo(C.Structure):
+    _fields_ = [("n_code_blocks", C.c_int32), ("n_cb", C.c_int32), ("elem_bytes", C.c_int32), ("reserved0", C.c_int32),
+                ("bytes_per_slot", C.c_int64)]
+
+
+class RmHostView(C.Structure):
+    _fields_ = [("b", C.c_int32), ("k_cb", C.c_int32), ("c", C.c_int32), ("b_prime", C.c_int32), ("k_prime", C.c_int32),
+                ("k_b", C.c_int32), ("zc", C.c_int32), ("k", C.c_int32), ("n", C.c_int32), ("n_cb", C.c_int32),
+                ("f0", C.c_int32), ("f1", C.c_int32), ("p", C.c_int32), ("n_lo", C.c_int32), ("e_lo", C.c_int32),
+                ("e_hi", C.c_int32), ("k0", C.c_int32 * 4), ("s", C.c_int32 * 4), ("unit_elems", C.c_int32),
+                ("tiles_per_block", C.c_int32), ("n_tiles", C.c_int32)]
+
+
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
 # VGPRs (the default AGPR form costs four v_accvgpr_read per 16x16 tile in a kernel bound by vector-instruction issue)
 EXTRA_FLAGS = {"ce_denoise.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
@@ -177,7 +201,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", INCLUDE / "ce_eq.h", INCLUDE / "ce_demod.h", Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", INCLUDE / "ce_eq.h", INCLUDE / "ce_demod.h", INCLUDE / "ce_rm.h", Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -291,6 +315,16 @@ def load() -> C.CDLL:
     lib.ce_demod_plan_get_info.restype = C.c_int
     lib.ce_demod_demap.argtypes = [vp, vp, vp, vp, vp, i64p, C.c_int64, vp, vp]
     lib.ce_demod_demap.restype = C.c_int
+    lib.ce_rm_derive_host.argtypes = [C.POINTER(RmDesc), C.POINTER(RmHostView)]
+    lib.ce_rm_derive_host.restype = C.c_int
+    lib.ce_rm_plan_create.argtypes = [C.POINTER(RmDesc), C.POINTER(vp)]
+    lib.ce_rm_plan_create.restype = C.c_int
+    lib.ce_rm_plan_destroy.argtypes = [vp]
+    lib.ce_rm_plan_destroy.restype = None
+    lib.ce_rm_plan_get_info.argtypes = [vp, C.POINTER(RmInfo)]
+    lib.ce_rm_plan_get_info.restype = C.c_int
+    lib.ce_rm_recover.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp]
+    lib.ce_rm_recover.restype = C.c_int
     if lib.ce_abi_version() != CE_ABI_VERSION:
         raise RuntimeError(f"libce_hip.so ABI {lib.ce_abi_version()} != binding {CE_ABI_VERSION}; rebuild")
     _lib = lib
