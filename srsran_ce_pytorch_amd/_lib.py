@@ -23,7 +23,8 @@ KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # units compile concurrently (ce_inst.inc)
 SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
-HEADERS = ["ce_plan.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
+HEADERS = ["ce_plan.h", "ce_stage.h", "ce_gold.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
+PUBLIC_HEADERS = ["ce_hip.h", "ce_denoise.h", "ce_dmrs.h", "ce_eq.h", "ce_demod.h", "ce_rm.h"]   # include/
 
 CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
@@ -73,11 +74,27 @@ KERNEL_UNITS = ["ce_inst_narrow.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f
                 "ce_inst_reg_h2_f0.hip", "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip"]
 
 
-EXPORTS = ["ce_plan_create", "ce_plan_destroy", "ce_plan_get_info", "ce_plan_derive_host", "ce_estimate_batch",
-           "ce_estimate_batch_stages", "ce_time_batch", "ce_last_error", "ce_abi_version"]
-EXPORTS_DENOISE = ["ce_denoiser_create", "ce_denoiser_destroy", "ce_denoise_batch"]   # include/ce_denoise.h (extension)
-EXPORTS_DMRS = ["ce_dmrs_derive_host", "ce_dmrs_plan_create", "ce_dmrs_plan_destroy", "ce_dmrs_plan_get_info",
-                "ce_dmrs_generate"]                                                       # include/ce_dmrs.h (extension)
+# One table per public header: entry point -> (restype, argtypes).  load() applies them; the EXPORTS_* lists are their keys.
+_int, _vp, _i64, _i32 = C.c_int, C.c_void_p, C.c_int64, C.c_int32
+_i64p, _fp, _P = C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER
+_BATCH = [_vp, _vp, _i64p, _vp, _i64p, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+SIGNATURES = {                                                                            # include/ce_hip.h
+    "ce_plan_create": (_int, [_P(PlanDesc), _P(_vp)]),
+    "ce_plan_destroy": (None, [_vp]),
+    "ce_plan_get_info": (_int, [_vp, _P(PlanInfo)]),
+    "ce_plan_derive_host": (_int, [_P(PlanDesc), _P(PlanHostView)]),
+    "ce_estimate_batch": (_int, _BATCH),
+    "ce_estimate_batch_stages": (_int, _BATCH[:-1] + [_vp, _vp, _vp]),
+    "ce_time_batch": (_int, _BATCH + [_i32, _i32, _P(C.c_double)]),
+    "ce_last_error": (C.c_char_p, []),
+    "ce_abi_version": (_int, []),
+}
+SIGNATURES_DENOISE = {                                                                    # include/ce_denoise.h (extension)
+    "ce_denoiser_create": (_int, [_i32, _fp, _fp, _fp, _fp, _fp, _fp, _P(_vp)]),
+    "ce_denoiser_destroy": (None, [_vp]),
+    "ce_denoise_batch": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+}
+EXPORTS, EXPORTS_DENOISE = list(SIGNATURES), list(SIGNATURES_DENOISE)
 CE_DMRS_MAX_WORDS, CE_DMRS_MAX_RE = 136, 2048
 
 
@@ -106,8 +123,14 @@ class DmrsHostView(C.Structure):
                 ("odd_sign", (C.c_uint8 * CE_DMRS_MAX_RE) * CE_MAX_HOPS)]
 
 
-EXPORTS_EQ = ["ce_eq_derive_host", "ce_eq_plan_create", "ce_eq_plan_destroy", "ce_eq_plan_get_info",
-              "ce_eq_equalize"]                                                           # include/ce_eq.h (extension)
+SIGNATURES_DMRS = {                                                                       # include/ce_dmrs.h (extension)
+    "ce_dmrs_derive_host": (_int, [_P(DmrsDesc), _P(DmrsHostView)]),
+    "ce_dmrs_plan_create": (_int, [_P(DmrsDesc), _P(_vp)]),
+    "ce_dmrs_plan_destroy": (None, [_vp]),
+    "ce_dmrs_plan_get_info": (_int, [_vp, _P(DmrsInfo)]),
+    "ce_dmrs_generate": (_int, [_vp, _vp, _vp, _vp, _i64p, _i64, _vp, _vp]),
+}
+EXPORTS_DMRS = list(SIGNATURES_DMRS)
 CE_EQ_MAX_PORTS, CE_EQ_CHUNK_SC = 8, 36
 
 
@@ -131,8 +154,14 @@ class EqHostView(C.Structure):
                 ("n_data_re", C.c_int32)]
 
 
-EXPORTS_DEMOD = ["ce_demod_derive_host", "ce_demod_copy_tables", "ce_demod_plan_create", "ce_demod_plan_destroy",
-                 "ce_demod_plan_get_info", "ce_demod_demap"]                              # include/ce_demod.h (extension)
+SIGNATURES_EQ = {                                                                         # include/ce_eq.h (extension)
+    "ce_eq_derive_host": (_int, [_P(EqDesc), _P(EqHostView)]),
+    "ce_eq_plan_create": (_int, [_P(EqDesc), _P(_vp)]),
+    "ce_eq_plan_destroy": (None, [_vp]),
+    "ce_eq_plan_get_info": (_int, [_vp, _P(EqInfo)]),
+    "ce_eq_equalize": (_int, [_vp, _vp, _i64p, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+}
+EXPORTS_EQ = list(SIGNATURES_EQ)
 CE_DEMOD_MAX_BITS, CE_DEMOD_BLOCK_WORDS, CE_DEMOD_TILE_SYMBOLS = 1 << 21, 8, 1024
 CE_DEMOD_OUT_F32, CE_DEMOD_OUT_I8 = 0, 1
 
@@ -151,8 +180,15 @@ class DemodHostView(C.Structure):
                 ("tile_symbols", C.c_int32), ("n_tiles", C.c_int32), ("table_bytes", C.c_int64)]
 
 
-EXPORTS_RM = ["ce_rm_derive_host", "ce_rm_plan_create", "ce_rm_plan_destroy", "ce_rm_plan_get_info",
-              "ce_rm_recover"]                                                            # include/ce_rm.h (extension)
+SIGNATURES_DEMOD = {                                                                      # include/ce_demod.h (extension)
+    "ce_demod_derive_host": (_int, [_P(DemodDesc), _P(DemodHostView)]),
+    "ce_demod_copy_tables": (_int, [_P(DemodDesc), _vp, _vp]),
+    "ce_demod_plan_create": (_int, [_P(DemodDesc), _P(_vp)]),
+    "ce_demod_plan_destroy": (None, [_vp]),
+    "ce_demod_plan_get_info": (_int, [_vp, _P(DemodInfo)]),
+    "ce_demod_demap": (_int, [_vp, _vp, _vp, _vp, _vp, _i64p, _i64, _vp, _vp]),
+}
+EXPORTS_DEMOD = list(SIGNATURES_DEMOD)
 CE_RM_F32, CE_RM_I8, CE_RM_MAX_SLOT_ELEMS, CE_RM_TILE_UNITS = 0, 1, 1 << 24, 1024
 
 
@@ -173,6 +209,16 @@ class RmHostView(C.Structure):
                 ("f0", C.c_int32), ("f1", C.c_int32), ("p", C.c_int32), ("n_lo", C.c_int32), ("e_lo", C.c_int32),
                 ("e_hi", C.c_int32), ("k0", C.c_int32 * 4), ("s", C.c_int32 * 4), ("unit_elems", C.c_int32),
                 ("tiles_per_block", C.c_int32), ("n_tiles", C.c_int32)]
+
+
+SIGNATURES_RM = {                                                                         # include/ce_rm.h (extension)
+    "ce_rm_derive_host": (_int, [_P(RmDesc), _P(RmHostView)]),
+    "ce_rm_plan_create": (_int, [_P(RmDesc), _P(_vp)]),
+    "ce_rm_plan_destroy": (None, [_vp]),
+    "ce_rm_plan_get_info": (_int, [_vp, _P(RmInfo)]),
+    "ce_rm_recover": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+}
+EXPORTS_RM = list(SIGNATURES_RM)
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -201,7 +247,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / "ce_hip.h", INCLUDE / "ce_denoise.h", INCLUDE / "ce_dmrs.h", INCLUDE / "ce_eq.h", INCLUDE / "ce_demod.h", INCLUDE / "ce_rm.h", Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS] + [Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -256,75 +302,10 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the estimator has no CPU fallback)")
     lib = C.CDLL(str(LIB_PATH))
-    vp, i64p, dp = C.c_void_p, C.POINTER(C.c_int64), C.c_void_p
-    lib.ce_plan_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(vp)]
-    lib.ce_plan_create.restype = C.c_int
-    lib.ce_plan_destroy.argtypes = [vp]
-    lib.ce_plan_destroy.restype = None
-    lib.ce_plan_get_info.argtypes = [vp, C.POINTER(PlanInfo)]
-    lib.ce_plan_get_info.restype = C.c_int
-    lib.ce_plan_derive_host.argtypes = [C.POINTER(PlanDesc), C.POINTER(PlanHostView)]
-    lib.ce_plan_derive_host.restype = C.c_int
-    batch = [vp, vp, i64p, vp, i64p, C.c_int64, C.c_int32, vp, dp, dp, dp, dp, dp, vp]
-    lib.ce_estimate_batch.argtypes = batch
-    lib.ce_estimate_batch.restype = C.c_int
-    lib.ce_estimate_batch_stages.argtypes = batch[:-1] + [vp, dp, vp]
-    lib.ce_estimate_batch_stages.restype = C.c_int
-    lib.ce_time_batch.argtypes = batch + [C.c_int32, C.c_int32, C.POINTER(C.c_double)]
-    lib.ce_time_batch.restype = C.c_int
-    lib.ce_last_error.argtypes = []
-    lib.ce_last_error.restype = C.c_char_p
-    lib.ce_abi_version.argtypes = []
-    lib.ce_abi_version.restype = C.c_int
-    fp = C.POINTER(C.c_float)
-    lib.ce_denoiser_create.argtypes = [C.c_int32, fp, fp, fp, fp, fp, fp, C.POINTER(vp)]
-    lib.ce_denoiser_create.restype = C.c_int
-    lib.ce_denoiser_destroy.argtypes = [vp]
-    lib.ce_denoiser_destroy.restype = None
-    lib.ce_denoise_batch.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ce_denoise_batch.restype = C.c_int
-    lib.ce_dmrs_derive_host.argtypes = [C.POINTER(DmrsDesc), C.POINTER(DmrsHostView)]
-    lib.ce_dmrs_derive_host.restype = C.c_int
-    lib.ce_dmrs_plan_create.argtypes = [C.POINTER(DmrsDesc), C.POINTER(vp)]
-    lib.ce_dmrs_plan_create.restype = C.c_int
-    lib.ce_dmrs_plan_destroy.argtypes = [vp]
-    lib.ce_dmrs_plan_destroy.restype = None
-    lib.ce_dmrs_plan_get_info.argtypes = [vp, C.POINTER(DmrsInfo)]
-    lib.ce_dmrs_plan_get_info.restype = C.c_int
-    lib.ce_dmrs_generate.argtypes = [vp, vp, vp, vp, i64p, C.c_int64, vp, vp]
-    lib.ce_dmrs_generate.restype = C.c_int
-    lib.ce_eq_derive_host.argtypes = [C.POINTER(EqDesc), C.POINTER(EqHostView)]
-    lib.ce_eq_derive_host.restype = C.c_int
-    lib.ce_eq_plan_create.argtypes = [C.POINTER(EqDesc), C.POINTER(vp)]
-    lib.ce_eq_plan_create.restype = C.c_int
-    lib.ce_eq_plan_destroy.argtypes = [vp]
-    lib.ce_eq_plan_destroy.restype = None
-    lib.ce_eq_plan_get_info.argtypes = [vp, C.POINTER(EqInfo)]
-    lib.ce_eq_plan_get_info.restype = C.c_int
-    lib.ce_eq_equalize.argtypes = [vp, vp, i64p, vp, vp, C.c_int64, C.c_int32, vp, vp, vp]
-    lib.ce_eq_equalize.restype = C.c_int
-    lib.ce_demod_derive_host.argtypes = [C.POINTER(DemodDesc), C.POINTER(DemodHostView)]
-    lib.ce_demod_derive_host.restype = C.c_int
-    lib.ce_demod_copy_tables.argtypes = [C.POINTER(DemodDesc), vp, vp]
-    lib.ce_demod_copy_tables.restype = C.c_int
-    lib.ce_demod_plan_create.argtypes = [C.POINTER(DemodDesc), C.POINTER(vp)]
-    lib.ce_demod_plan_create.restype = C.c_int
-    lib.ce_demod_plan_destroy.argtypes = [vp]
-    lib.ce_demod_plan_destroy.restype = None
-    lib.ce_demod_plan_get_info.argtypes = [vp, C.POINTER(DemodInfo)]
-    lib.ce_demod_plan_get_info.restype = C.c_int
-    lib.ce_demod_demap.argtypes = [vp, vp, vp, vp, vp, i64p, C.c_int64, vp, vp]
-    lib.ce_demod_demap.restype = C.c_int
-    lib.ce_rm_derive_host.argtypes = [C.POINTER(RmDesc), C.POINTER(RmHostView)]
-    lib.ce_rm_derive_host.restype = C.c_int
-    lib.ce_rm_plan_create.argtypes = [C.POINTER(RmDesc), C.POINTER(vp)]
-    lib.ce_rm_plan_create.restype = C.c_int
-    lib.ce_rm_plan_destroy.argtypes = [vp]
-    lib.ce_rm_plan_destroy.restype = None
-    lib.ce_rm_plan_get_info.argtypes = [vp, C.POINTER(RmInfo)]
-    lib.ce_rm_plan_get_info.restype = C.c_int
-    lib.ce_rm_recover.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp]
-    lib.ce_rm_recover.restype = C.c_int
+    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     if lib.ce_abi_version() != CE_ABI_VERSION:
         raise RuntimeError(f"libce_hip.so ABI {lib.ce_abi_version()} != binding {CE_ABI_VERSION}; rebuild")
     _lib = lib

@@ -4,8 +4,8 @@
 // Gold sequence.  c = x1 ^ x2, x1 does not depend on c_init and x2 is linear over GF(2) in it.  The host derives once per
 // plan the words of x1 (at Nc = 1600) for the whole codeword and, per block of DQ_BW = 8 words, the 31-bit x2 state at the
 // block's first bit for each c_init = 1 << i (the jump entries).  A thread XORs the entries of the set bits of c_init and
-// steps the x2 recurrence a word at a time through its own block only: nobody walks from n = 0, the cost of a bit does not
-// depend on Nc or on where the bit sits in the codeword.  Tables: DESIGN 6f.
+// steps the x2 recurrence a word at a time (ce_gold.h) through its own block only: nobody walks from n = 0, the cost of a
+// bit does not depend on Nc or on where the bit sits in the codeword.  Tables: DESIGN 6f.
 //
 // Kernel: one 256-thread workgroup per slot and tile of DQ_TILE = 1024 symbols (32 Qm words of c = 4 Qm whole blocks).
 //   1. every thread issues the loads of its two pairs of neighbouring symbols (a 16-byte load of x_hat and an 8-byte load
@@ -29,14 +29,14 @@
 #include <vector>
 
 #include "ce_demod.h"
-#include "ce_plan.h"
+#include "ce_gold.h"
+#include "ce_stage.h"
 
 namespace {
 
 constexpr int DQ_NT = 256;
 constexpr int DQ_TILE = CE_DEMOD_TILE_SYMBOLS;
 constexpr int DQ_BW = CE_DEMOD_BLOCK_WORDS;
-constexpr int DQ_NC_WORDS = 50;   // Nc = 1600 = 50 words (38.211 5.2.1)
 static_assert(DQ_TILE == 4 * DQ_NT && (DQ_TILE * 2 / 32) % DQ_BW == 0, "a tile is two pairs per thread and whole Gold blocks");
 
 struct DemodDev {
@@ -46,19 +46,6 @@ struct DemodDev {
   uint32_t n_blocks;   // Gold blocks per slot (0: no descrambling)
   float scale;         // llr_scale
 };
-
-// One word (32 steps) of a length-31 LFSR whose feedback is x(n + 31) = XOR of x(n + t) over the taps: x1 has taps {0, 3},
-// x2 {0, 1, 2, 3}.  `s` holds x(n .. n + 30) in bits 0 .. 30; returns x(n .. n + 31) and leaves x(n + 32 .. n + 62) in s.
-template <bool IS_X2>
-__host__ __device__ __forceinline__ uint32_t dq_step_word(uint32_t& s) {
-  uint64_t v = s;
-  uint64_t t = IS_X2 ? v ^ (v >> 1) ^ (v >> 2) ^ (v >> 3) : v ^ (v >> 3);
-  v |= (t & 0x0FFFFFFFull) << 31;                        // x(n + 31 .. n + 58) from x(n .. n + 30)
-  t = IS_X2 ? v ^ (v >> 1) ^ (v >> 2) ^ (v >> 3) : v ^ (v >> 3);
-  v |= ((t >> 28) & 0xFull) << 59;                       // x(n + 59 .. n + 62) from x(n + 28 .. n + 34)
-  s = (uint32_t)(v >> 32) & 0x7FFFFFFFu;
-  return (uint32_t)v;
-}
 
 // Sign-bit LLR of a Gray PAM axis with levels +-1, +-3, .. +-K in units of A^2: (distance to the nearest negative level)^2
 // - (distance to the nearest positive level)^2 for v >= 0, odd in v.
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(DQ_NT) void ce_demod_kernel(DemodDev P, const uint3
         w[4 * q + 3] = x.w;
       }
 #pragma unroll
-      for (int k = 0; k < DQ_BW; ++k) cw[tid * DQ_BW + k] = w[k] ^ dq_step_word<true>(s);
+      for (int k = 0; k < DQ_BW; ++k) cw[tid * DQ_BW + k] = w[k] ^ ce_gold_step_word<true>(s);
     }
     __syncthreads();
   }
@@ -292,15 +279,12 @@ void dq_tables(const ce_demod_host_view& v, std::vector<uint32_t>& x1, std::vect
   const size_t nb = (size_t)v.n_blocks, nw = nb * DQ_BW;
   x1.assign(nw, 0u);
   jump.assign(nb * 31, 0u);
-  uint32_t s = 1u;   // x1(0) = 1, x1(1 .. 30) = 0
-  for (int w = 0; w < DQ_NC_WORDS; ++w) (void)dq_step_word<false>(s);
-  for (size_t w = 0; w < nw; ++w) x1[w] = dq_step_word<false>(s);
+  if (nw) ce_gold_words<false>(1u, 0, (int)nw - 1, x1.data());   // x1(0) = 1, x1(1 .. 30) = 0
   for (int i = 0; i < 31; ++i) {
-    s = 1u << i;
-    for (int w = 0; w < DQ_NC_WORDS; ++w) (void)dq_step_word<true>(s);
+    uint32_t s = ce_gold_state_at<true>(1u << i, 0);
     for (size_t blk = 0; blk < nb; ++blk) {
       jump[blk * 31 + i] = s;
-      for (int k = 0; k < DQ_BW; ++k) (void)dq_step_word<true>(s);
+      for (int k = 0; k < DQ_BW; ++k) (void)ce_gold_step_word<true>(s);
     }
   }
 }
@@ -338,7 +322,7 @@ extern "C" int ce_demod_plan_create(const ce_demod_desc* d, ce_demod_plan** out)
   if (!d || !out) return ce_fail(CE_ERR_INVALID, "null argument");
   ce_demod_host_view v;
   if (const int rc = dq_derive(d, &v); rc != CE_OK) return rc;
-  std::unique_ptr<ce_demod_plan> p(new (std::nothrow) ce_demod_plan);
+  auto p = ce_new_plan<ce_demod_plan>();
   if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
   p->device = d->device;
   p->qm = d->qm;
@@ -360,11 +344,8 @@ extern "C" int ce_demod_plan_create(const ce_demod_desc* d, ce_demod_plan** out)
   for (int blk = 0; blk < v.n_blocks; ++blk)
     for (int i = 0; i < 31; ++i) rows[(size_t)i * v.n_blocks + blk] = j[(size_t)blk * 31 + i];
   CeDeviceScope scope(d->device);
-  hipError_t e = scope.err;
-  if (e == hipSuccess) e = hipMalloc(&p->x1, x1.size() * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&p->jump, rows.size() * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(p->x1, x1.data(), x1.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->jump, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  hipError_t e = ce_upload(scope.err, &p->x1, x1.data(), x1.size() * sizeof(uint32_t));
+  e = ce_upload(e, &p->jump, rows.data(), rows.size() * sizeof(uint32_t));
   if (e != hipSuccess) {
     ce_demod_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "demapper plan upload: %s", hipGetErrorString(e));
@@ -380,11 +361,7 @@ extern "C" void ce_demod_plan_destroy(ce_demod_plan* p) {
   delete p;
 }
 
-extern "C" int ce_demod_plan_get_info(const ce_demod_plan* p, ce_demod_info* info) {
-  if (!p || !info) return ce_fail(CE_ERR_INVALID, "null argument");
-  *info = p->info;
-  return CE_OK;
-}
+extern "C" int ce_demod_plan_get_info(const ce_demod_plan* p, ce_demod_info* info) { return ce_get_info(p, info); }
 
 extern "C" int ce_demod_demap(const ce_demod_plan* p, const void* x_hat, const float* nvar, const int32_t* rnti, const int32_t* n_id,
                               const int64_t strides[2], int64_t n_slots, void* out, void* stream) {
@@ -399,7 +376,7 @@ extern "C" int ce_demod_demap(const ce_demod_plan* p, const void* x_hat, const f
     return ce_fail(CE_ERR_INVALID, "x_hat, nvar and out must be 16-byte aligned");
   if (n_slots * (int64_t)p->dev.n_tiles > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u tiles: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.n_tiles);
   CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_fail(CE_ERR_HIP, "device %d: %s", p->device, hipGetErrorString(scope.err));
+  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
   const unsigned n_wg = (unsigned)(n_slots * p->dev.n_tiles);
   const float2* x = reinterpret_cast<const float2*>(x_hat);
   const int64_t s0 = descramble ? strides[0] : 0, s1 = descramble ? strides[1] : 0;
@@ -410,6 +387,5 @@ extern "C" int ce_demod_demap(const ce_demod_plan* p, const void* x_hat, const f
     case 6: dq_launch<6>(p->dev, p->i8, n_wg, p->x1, p->jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
     default: dq_launch<8>(p->dev, p->i8, n_wg, p->x1, p->jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CE_OK : ce_fail(CE_ERR_HIP, "demapper launch: %s", hipGetErrorString(e));
+  return ce_launch_status("demapper");
 }

@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "ce_denoise.h"
-#include "ce_plan.h"
+#include "ce_stage.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -387,11 +387,8 @@ extern "C" int ce_denoiser_create(int32_t device, const float* w1, const float* 
   ce_denoiser* d = new ce_denoiser;
   d->device = device;
   CeDeviceScope scope(device);
-  hipError_t e = scope.err;
-  if (e == hipSuccess) e = hipMalloc(&d->wfrag, frag.size() * sizeof(_Float16));
-  if (e == hipSuccess) e = hipMalloc(&d->bias, sizeof(bias));
-  if (e == hipSuccess) e = hipMemcpy(d->wfrag, frag.data(), frag.size() * sizeof(_Float16), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d->bias, bias, sizeof(bias), hipMemcpyHostToDevice);
+  hipError_t e = ce_upload(scope.err, &d->wfrag, frag.data(), frag.size() * sizeof(_Float16));
+  e = ce_upload(e, &d->bias, bias, sizeof(bias));
   if (e != hipSuccess) {
     ce_denoiser_destroy(d);
     return ce_fail(CE_ERR_HIP, "denoiser upload: %s", hipGetErrorString(e));
@@ -416,9 +413,8 @@ extern "C" int ce_denoise_batch(const ce_denoiser* d, void* ch_est, int64_t n_it
   if (planes == 0) return CE_OK;
   if (planes > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld planes in one launch", (long long)planes);
   CeDeviceScope scope(d->device);
-  if (scope.err != hipSuccess) return ce_fail(CE_ERR_HIP, "device %d: %s", d->device, hipGetErrorString(scope.err));
+  if (scope.err != hipSuccess) return ce_device_fail(d->device, scope.err);
   hipLaunchKernelGGL(ce_denoise_kernel, dim3((unsigned)planes), dim3(DN_NT), 0, (hipStream_t)stream,
                      reinterpret_cast<float2*>(ch_est), d->wfrag, d->bias, n_sc, n_layers);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CE_OK : ce_fail(CE_ERR_HIP, "denoise launch: %s", hipGetErrorString(e));
+  return ce_launch_status("denoise");
 }

@@ -4,9 +4,9 @@
 // The Gold generator of TS 38.211 5.2.1 is linear over GF(2) in c_init: word w of c is
 //     X1[w] ^ XOR over the set bits i of c_init of T[i][w]
 // with X1 = the words of c for c_init = 0 and T[i] = the words for c_init = 1 << i, XORed with X1.  The host derives both
-// once per plan (bit-serial, integer only) for the words a hop's pilots touch and uploads them as rows of one table per
-// hop: row 0 = X1, rows 1 .. 31 = T[0 .. 30], row 32 = zeros.  No thread ever steps the recurrence: the cost of a pilot
-// does not depend on Nc = 1600 or on where the allocation sits in the carrier.
+// once per plan (ce_gold.h: a word at a time, integer only) for the words a hop's pilots touch and uploads them as rows of
+// one table per hop: row 0 = X1, rows 1 .. 31 = T[0 .. 30], row 32 = zeros.  No thread ever steps the recurrence: the cost
+// of a pilot does not depend on Nc = 1600 or on where the allocation sits in the carrier.
 //
 // Kernel: one 256-thread workgroup per slot.
 //   1. per DM-RS column (c_init is uniform over the workgroup), thread w builds word w of the column's c into the LDS:
@@ -24,13 +24,13 @@
 #include <vector>
 
 #include "ce_dmrs.h"
-#include "ce_plan.h"
+#include "ce_gold.h"
+#include "ce_stage.h"
 
 namespace {
 
 constexpr int DM_NT = 256;
 constexpr int DM_ROWS = 33;          // table rows per hop: X1, T[0..30], zeros
-constexpr int DM_NC = 1600;          // 38.211 5.2.1
 constexpr uint32_t DM_A = 0x3f3504f3u;  // float32 0.70710677
 
 struct DmrsDev {
@@ -142,22 +142,6 @@ int dm_mask_ppp(unsigned m) {
   return 0;
 }
 
-// Words w_lo .. w_hi of c for one of the two m-sequences alone (the other all zero): x1 (x1(n+31) = x1(n+3) ^ x1(n)) or
-// x2 (x2(n+31) = x2(n+3) ^ x2(n+2) ^ x2(n+1) ^ x2(n)), state bit j = x(n + j).
-void dm_lfsr_words(uint32_t init, bool is_x2, int w_lo, int w_hi, uint32_t* out) {
-  uint32_t s = init & 0x7FFFFFFFu;
-  const int64_t first = 32ll * w_lo + DM_NC, last = 32ll * (w_hi + 1) + DM_NC;
-  for (int i = 0; i <= w_hi - w_lo; ++i) out[i] = 0u;
-  for (int64_t n = 0; n < last; ++n) {
-    if (n >= first && (s & 1u)) {
-      const int64_t c = n - DM_NC;
-      out[c / 32 - w_lo] |= 1u << (c % 32);
-    }
-    const uint32_t nb = (is_x2 ? (s >> 3) ^ (s >> 2) ^ (s >> 1) ^ s : (s >> 3) ^ s) & 1u;
-    s = (s >> 1) | (nb << 30);
-  }
-}
-
 int dm_derive(const ce_dmrs_desc* d, ce_dmrs_host_view* v) {
   memset(v, 0, sizeof(*v));
   if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
@@ -208,8 +192,8 @@ int dm_derive(const ce_dmrs_desc* d, ce_dmrs_host_view* v) {
     if (w_hi - w_lo + 1 > CE_DMRS_MAX_WORDS) return ce_fail(CE_ERR_UNSUPPORTED, "hop %d spans %d words of the sequence (> %d)", h, w_hi - w_lo + 1, CE_DMRS_MAX_WORDS);
     v->word0[h] = w_lo;
     v->n_words[h] = w_hi - w_lo + 1;
-    dm_lfsr_words(1u, false, w_lo, w_hi, v->x1[h]);
-    for (int i = 0; i < 31; ++i) dm_lfsr_words(1u << i, true, w_lo, w_hi, v->t[h][i]);
+    ce_gold_words<false>(1u, w_lo, w_hi, v->x1[h]);
+    for (int i = 0; i < 31; ++i) ce_gold_words<true>(1u << i, w_lo, w_hi, v->t[h][i]);
   }
   v->n_re = n_active0 * ppp;
   v->n_dmrs_total = n_cols;
@@ -229,7 +213,7 @@ extern "C" int ce_dmrs_plan_create(const ce_dmrs_desc* d, ce_dmrs_plan** out) {
   std::unique_ptr<ce_dmrs_host_view> v(new (std::nothrow) ce_dmrs_host_view);
   if (!v) return ce_fail(CE_ERR_NOMEM, "out of host memory");
   if (const int rc = dm_derive(d, v.get()); rc != CE_OK) return rc;
-  std::unique_ptr<ce_dmrs_plan> p(new (std::nothrow) ce_dmrs_plan);
+  auto p = ce_new_plan<ce_dmrs_plan>();
   if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
   p->device = d->device;
   p->n_layers = d->n_layers;
@@ -262,11 +246,8 @@ extern "C" int ce_dmrs_plan_create(const ce_dmrs_desc* d, ce_dmrs_plan** out) {
     for (int k = 0; k < v->n_re; ++k) ptab[(size_t)h * v->n_re + k] = (uint16_t)(2 * v->m[h][k] - 32 * v->word0[h]);   // < 32 * CE_DMRS_MAX_WORDS
   }
   CeDeviceScope scope(d->device);
-  hipError_t e = scope.err;
-  if (e == hipSuccess) e = hipMalloc(&p->tab, tab.size() * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&p->ptab, ptab.size() * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMemcpy(p->tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->ptab, ptab.data(), ptab.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  hipError_t e = ce_upload(scope.err, &p->tab, tab.data(), tab.size() * sizeof(uint32_t));
+  e = ce_upload(e, &p->ptab, ptab.data(), ptab.size() * sizeof(uint16_t));
   if (e != hipSuccess) {
     ce_dmrs_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "DM-RS plan upload: %s", hipGetErrorString(e));
@@ -282,11 +263,7 @@ extern "C" void ce_dmrs_plan_destroy(ce_dmrs_plan* p) {
   delete p;
 }
 
-extern "C" int ce_dmrs_plan_get_info(const ce_dmrs_plan* p, ce_dmrs_info* info) {
-  if (!p || !info) return ce_fail(CE_ERR_INVALID, "null argument");
-  *info = p->info;
-  return CE_OK;
-}
+extern "C" int ce_dmrs_plan_get_info(const ce_dmrs_plan* p, ce_dmrs_info* info) { return ce_get_info(p, info); }
 
 extern "C" int ce_dmrs_generate(const ce_dmrs_plan* p, const int32_t* slot, const int32_t* n_id, const int32_t* n_scid,
                                 const int64_t strides[3], int64_t n_slots, void* pilots_out, void* stream) {
@@ -297,7 +274,7 @@ extern "C" int ce_dmrs_generate(const ce_dmrs_plan* p, const int32_t* slot, cons
   if (strides[0] < 0 || strides[1] < 0 || strides[2] < 0) return ce_fail(CE_ERR_INVALID, "negative strides are not supported");
   if (n_slots > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "more than 2^31-1 slots in one launch");
   CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_fail(CE_ERR_HIP, "device %d: %s", p->device, hipGetErrorString(scope.err));
+  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
   const bool vec2 = p->dev.n_elem % 2 == 0 && (reinterpret_cast<uintptr_t>(pilots_out) & 15u) == 0;
   float2* out = reinterpret_cast<float2*>(pilots_out);
   const hipStream_t st = (hipStream_t)stream;
@@ -307,6 +284,5 @@ extern "C" int ce_dmrs_generate(const ce_dmrs_plan* p, const int32_t* slot, cons
     case 3: dm_launch<3>(p, vec2, (unsigned)n_slots, slot, n_id, n_scid, strides, out, st); break;
     default: dm_launch<4>(p, vec2, (unsigned)n_slots, slot, n_id, n_scid, strides, out, st); break;
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CE_OK : ce_fail(CE_ERR_HIP, "DM-RS launch: %s", hipGetErrorString(e));
+  return ce_launch_status("DM-RS");
 }

@@ -21,7 +21,7 @@
 #include <memory>
 
 #include "ce_eq.h"
-#include "ce_plan.h"
+#include "ce_stage.h"
 
 namespace {
 
@@ -367,7 +367,7 @@ extern "C" int ce_eq_plan_create(const ce_eq_desc* d, ce_eq_plan** out) {
   if (!d || !out) return ce_fail(CE_ERR_INVALID, "null argument");
   ce_eq_host_view v;
   if (const int rc = eq_derive(d, &v); rc != CE_OK) return rc;
-  std::unique_ptr<ce_eq_plan> p(new (std::nothrow) ce_eq_plan);
+  auto p = ce_new_plan<ce_eq_plan>();
   if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
   p->device = d->device;
   p->n_layers = d->n_layers;
@@ -395,9 +395,7 @@ extern "C" int ce_eq_plan_create(const ce_eq_desc* d, ce_eq_plan** out) {
   P.chunk0 = sc_lo / EQ_CH;
   P.n_chunks = (sc_hi + EQ_CH - 1) / EQ_CH - P.chunk0;
   CeDeviceScope scope(d->device);
-  hipError_t e = scope.err;
-  if (e == hipSuccess) e = hipMalloc(&p->symtab, sizeof(tab));
-  if (e == hipSuccess) e = hipMemcpy(p->symtab, tab, sizeof(tab), hipMemcpyHostToDevice);
+  const hipError_t e = ce_upload(scope.err, &p->symtab, tab, sizeof(tab));
   if (e != hipSuccess) {
     ce_eq_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "equalizer plan upload: %s", hipGetErrorString(e));
@@ -412,11 +410,7 @@ extern "C" void ce_eq_plan_destroy(ce_eq_plan* p) {
   delete p;
 }
 
-extern "C" int ce_eq_plan_get_info(const ce_eq_plan* p, ce_eq_info* info) {
-  if (!p || !info) return ce_fail(CE_ERR_INVALID, "null argument");
-  *info = p->info;
-  return CE_OK;
-}
+extern "C" int ce_eq_plan_get_info(const ce_eq_plan* p, ce_eq_info* info) { return ce_get_info(p, info); }
 
 extern "C" int ce_eq_equalize(const ce_eq_plan* p, const void* rx, const int64_t rx_strides[4], const void* ch_est, const double* noise,
                               int64_t n_slots, int32_t n_ports, void* x_hat, float* nvar, void* stream) {
@@ -431,7 +425,7 @@ extern "C" int ce_eq_equalize(const ce_eq_plan* p, const void* rx, const int64_t
     return ce_fail(CE_ERR_INVALID, "ch_est, x_hat and nvar must be 16-byte aligned");
   if (n_slots * (int64_t)p->dev.n_chunks > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "more than 2^31-1 workgroups in one launch");
   CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_fail(CE_ERR_HIP, "device %d: %s", p->device, hipGetErrorString(scope.err));
+  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
   const unsigned n_wg = (unsigned)(n_slots * (int64_t)p->dev.n_chunks);
   const size_t lds = eq_lds_bytes(p->dev, p->n_layers, n_ports);
   const uint32_t sym_fast = rx_strides[3] < rx_strides[2] ? 1u : 0u;   // walk rx along its shorter stride
@@ -445,6 +439,5 @@ extern "C" int ce_eq_equalize(const ce_eq_plan* p, const void* rx, const int64_t
     case 3: eq_launch<3>(p, n_wg, lds, rxp, rx_strides, sym_fast, chp, noise, (uint32_t)n_ports, xo, nvar, st); break;
     default: eq_launch<4>(p, n_wg, lds, rxp, rx_strides, sym_fast, chp, noise, (uint32_t)n_ports, xo, nvar, st); break;
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CE_OK : ce_fail(CE_ERR_HIP, "equalizer launch: %s", hipGetErrorString(e));
+  return ce_launch_status("equalizer");
 }

@@ -1,0 +1,36 @@
+// The Gold sequence of TS 38.211 5.2.1, c(n) = x1(n + Nc) ^ x2(n + Nc), a word (32 bits) at a time.  The one generator of
+// the DM-RS tables (ce_dmrs.hip), the descrambling tables and the demapper's kernel (ce_demod.hip); DESIGN 6d.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+constexpr int CE_GOLD_NC_WORDS = 50;   // Nc = 1600 bits = 50 words
+
+// One word (32 steps) of a length-31 LFSR whose feedback is x(n + 31) = XOR of x(n + t) over the taps: x1 has taps {0, 3},
+// x2 {0, 1, 2, 3}.  `s` holds x(n .. n + 30) in bits 0 .. 30; returns x(n .. n + 31) and leaves x(n + 32 .. n + 62) in s.
+template <bool IS_X2>
+__host__ __device__ __forceinline__ uint32_t ce_gold_step_word(uint32_t& s) {
+  uint64_t v = s;
+  uint64_t t = IS_X2 ? v ^ (v >> 1) ^ (v >> 2) ^ (v >> 3) : v ^ (v >> 3);
+  v |= (t & 0x0FFFFFFFull) << 31;                        // x(n + 31 .. n + 58) from x(n .. n + 30)
+  t = IS_X2 ? v ^ (v >> 1) ^ (v >> 2) ^ (v >> 3) : v ^ (v >> 3);
+  v |= ((t >> 28) & 0xFull) << 59;                       // x(n + 59 .. n + 62) from x(n + 28 .. n + 34)
+  s = (uint32_t)(v >> 32) & 0x7FFFFFFFu;
+  return (uint32_t)v;
+}
+
+// Host: the state x(32 w + Nc .. 32 w + Nc + 30) of one m-sequence at the first bit of word `w` of c, from its 31-bit
+// initial state x(0 .. 30) (x1: 1; x2: c_init).
+template <bool IS_X2>
+inline uint32_t ce_gold_state_at(uint32_t init, int w) {
+  uint32_t s = init & 0x7FFFFFFFu;
+  for (int i = 0; i < CE_GOLD_NC_WORDS + w; ++i) (void)ce_gold_step_word<IS_X2>(s);
+  return s;
+}
+
+// Host: words w_lo .. w_hi of c for one m-sequence alone (the other all zero) into out[0 .. w_hi - w_lo].
+template <bool IS_X2>
+inline void ce_gold_words(uint32_t init, int w_lo, int w_hi, uint32_t* out) {
+  uint32_t s = ce_gold_state_at<IS_X2>(init, w_lo);
+  for (int w = w_lo; w <= w_hi; ++w) out[w - w_lo] = ce_gold_step_word<IS_X2>(s);
+}

@@ -32,8 +32,8 @@
 #include <memory>
 #include <type_traits>
 
-#include "ce_plan.h"
 #include "ce_rm.h"
+#include "ce_stage.h"
 
 namespace {
 
@@ -273,7 +273,7 @@ extern "C" int ce_rm_plan_create(const ce_rm_desc* d, ce_rm_plan** out) {
   if (!d || !out) return ce_fail(CE_ERR_INVALID, "null argument");
   ce_rm_host_view v;
   if (const int rc = rm_derive(d, &v); rc != CE_OK) return rc;
-  std::unique_ptr<ce_rm_plan> p(new (std::nothrow) ce_rm_plan);
+  auto p = ce_new_plan<ce_rm_plan>();
   if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
   p->device = d->device;
   p->i8 = d->format == CE_RM_I8;
@@ -311,11 +311,7 @@ extern "C" int ce_rm_plan_create(const ce_rm_desc* d, ce_rm_plan** out) {
 
 extern "C" void ce_rm_plan_destroy(ce_rm_plan* p) { delete p; }
 
-extern "C" int ce_rm_plan_get_info(const ce_rm_plan* p, ce_rm_info* info) {
-  if (!p || !info) return ce_fail(CE_ERR_INVALID, "null argument");
-  *info = p->info;
-  return CE_OK;
-}
+extern "C" int ce_rm_plan_get_info(const ce_rm_plan* p, ce_rm_info* info) { return ce_get_info(p, info); }
 
 extern "C" int ce_rm_recover(const ce_rm_plan* p, const void* llr, const int32_t* rv, int64_t rv_stride, int64_t n_slots, const void* harq_in,
                              void* out, void* stream) {
@@ -329,12 +325,11 @@ extern "C" int ce_rm_recover(const ce_rm_plan* p, const void* llr, const int32_t
   const int64_t n_wg = (n_slots + 7) / 8 * 8 * (int64_t)p->dev.n_tiles;
   if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u tiles: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.n_tiles);
   CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_fail(CE_ERR_HIP, "device %d: %s", p->device, hipGetErrorString(scope.err));
+  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
   const hipStream_t st = (hipStream_t)stream;
   if (p->i8)
     hipLaunchKernelGGL((ce_rm_kernel<true>), dim3((unsigned)n_wg), dim3(RM_NT), 0, st, p->dev, llr, rv, rv_stride, (uint32_t)n_slots, harq_in, out);
   else
     hipLaunchKernelGGL((ce_rm_kernel<false>), dim3((unsigned)n_wg), dim3(RM_NT), 0, st, p->dev, llr, rv, rv_stride, (uint32_t)n_slots, harq_in, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CE_OK : ce_fail(CE_ERR_HIP, "rate recovery launch: %s", hipGetErrorString(e));
+  return ce_launch_status("rate recovery");
 }

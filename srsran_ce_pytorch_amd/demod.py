@@ -16,8 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .dmrs import _raise_for
+from . import _lib, _stage
 
 MODULATIONS = {"qpsk": 2, "16qam": 4, "64qam": 6, "256qam": 8}
 MAX_BITS = _lib.CE_DEMOD_MAX_BITS
@@ -48,13 +47,8 @@ def build_desc(modulation, n_symbols: int, out_dtype=torch.float32, llr_scale: f
 
 def derive_host(modulation, n_symbols: int, out_dtype=torch.float32, llr_scale: float = 1.0, descramble: bool = False) -> _lib.DemodHostView:
     """Host-only view of what a plan holds (``ce_demod_derive_host``); works without a GPU."""
-    lib = _lib.load()
     desc = build_desc(modulation, n_symbols, out_dtype, llr_scale, descramble)
-    view = _lib.DemodHostView()
-    rc = lib.ce_demod_derive_host(C.byref(desc), C.byref(view))
-    if rc != 0:
-        _raise_for(rc)
-    return view
+    return _stage.derive_host("ce_demod_derive_host", desc, _lib.DemodHostView())
 
 
 def gold_tables(modulation, n_symbols: int):
@@ -68,63 +62,31 @@ def gold_tables(modulation, n_symbols: int):
     jump = np.zeros((view.n_blocks, 31), np.uint32)
     rc = lib.ce_demod_copy_tables(C.byref(desc), C.c_void_p(x1.ctypes.data), C.c_void_p(jump.ctypes.data))
     if rc != 0:
-        _raise_for(rc)
+        _stage.raise_for(rc)
     return x1, jump
 
 
-class PuschDemapper:
-    """Validated on construction (no GPU needed); the device plan is created at the first launch."""
+class PuschDemapper(_stage.Stage):
+    _CREATE, _DESTROY, _LAUNCH = "ce_demod_plan_create", "ce_demod_plan_destroy", "ce_demod_demap"
+    _NOUN = "the demapper"
 
     def __init__(self, modulation, n_symbols: int, out_dtype=torch.float32, llr_scale: float = 1.0, descramble: bool = False,
                  device=None):
-        self._lib = _lib.load()
-        self._handle = None
+        super().__init__(device)
         self._args = (modulation, int(n_symbols), out_dtype, float(llr_scale), bool(descramble))
         view = derive_host(*self._args)
         self.qm, self.n_symbols, self.n_bits = modulation_order(modulation), int(n_symbols), int(view.n_bits)
         self.out_dtype, self.llr_scale, self.descramble = out_dtype, float(llr_scale), bool(descramble)
-        self._device_arg = device
-        self.device: Optional[torch.device] = None
 
-    def _plan(self):
-        if self._handle is None:
-            device = self._device_arg
-            device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-            if device.type != "cuda":
-                raise RuntimeError("the demapper runs on a ROCm GPU only (no CPU fallback)")
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            desc = build_desc(*self._args, device_index=device.index)
-            handle = C.c_void_p()
-            with torch.cuda.device(device):
-                rc = self._lib.ce_demod_plan_create(C.byref(desc), C.byref(handle))
-            if rc != 0:
-                _raise_for(rc)
-            self._handle, self.device = handle, device
-        return self._handle
-
-    def _param(self, name: str, value, B: int):
-        """-> an int32 device tensor of 1 or B elements; host ints are range-checked, device tensors taken as they are."""
-        dev = self.device
-        if isinstance(value, torch.Tensor):
-            if value.dtype != torch.int32 or value.dim() != 1 or value.shape[0] != B or value.device != dev:
-                raise ValueError(f"{name}: a tensor must be int32 of shape [{B}] on {dev}, got {value.dtype} {tuple(value.shape)} on {value.device}")
-            if value.stride(0) < 0:
-                raise ValueError("negative strides are not supported")
-            return value
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-            raise ValueError(f"{name}: expected an int or an int32 device tensor of shape [{B}]")
-        lo, hi = _RANGES[name]
-        if not lo <= int(value) <= hi:
-            raise ValueError(f"{name}={int(value)} outside {lo}..{hi}")
-        return torch.tensor([int(value)], dtype=torch.int32).to(dev)      # on the current stream, like the launch that reads it
+    def _build_desc(self, device_index: int):
+        return build_desc(*self._args, device_index=device_index)
 
     def __call__(self, x_hat: torch.Tensor, nvar: torch.Tensor, rnti=None, n_id=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``llr[B, n_symbols * Qm]`` (float32 or int8) on the current stream.  ``x_hat`` (complex64) and ``nvar``
         (float32) are dense ``[B, ...]`` tensors of ``n_symbols`` elements per slot, e.g. exactly as the equalizer
         returns them; ``rnti`` / ``n_id`` (needed with ``descramble=True``) are Python ints for the whole batch or int32
         device tensors of length ``B``; ``out`` may pass the result tensor to be overwritten."""
-        handle = self._plan()
+        self._plan()
         dev = self.device
         for name, t, dt in (("x_hat", x_hat, torch.complex64), ("nvar", nvar, torch.float32)):
             if not isinstance(t, torch.Tensor) or t.device != dev:
@@ -139,26 +101,13 @@ class PuschDemapper:
         shape = (B, self.n_bits)
         if out is None:
             out = torch.empty(shape, dtype=self.out_dtype, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != self.out_dtype or tuple(out.shape) != shape
-              or not out.is_contiguous() or out.device != dev):
-            raise ValueError(f"out must be a dense {self.out_dtype} tensor of shape {shape} on {dev}")
-        params = [self._param("rnti", rnti, B), self._param("n_id", n_id, B)] if self.descramble else []
+        else:
+            _stage.check_dense("out", out, self.out_dtype, shape, dev)
+        params = [_stage.batch_param(n, v, B, dev, *_RANGES[n]) for n, v in (("rnti", rnti), ("n_id", n_id))] if self.descramble else []
         if B == 0:
             return out                                           # empty batch: nothing to launch
-        for name, t in (("x_hat", x_hat), ("nvar", nvar), ("out", out)):
-            if t.data_ptr() % 16:
-                raise ValueError(f"{name} must be 16-byte aligned")
-        strides = (C.c_int64 * 2)(*[0 if p.shape[0] == 1 else int(p.stride(0)) for p in params]) if params else None
+        _stage.check_aligned(("x_hat", x_hat), ("nvar", nvar), ("out", out))
+        strides = (C.c_int64 * 2)(*[_stage.batch_stride(p) for p in params]) if params else None
         ptrs = [C.c_void_p(p.data_ptr()) for p in params] if params else [None, None]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = self._lib.ce_demod_demap(handle, C.c_void_p(x_hat.data_ptr()), C.c_void_p(nvar.data_ptr()), *ptrs, strides, B,
-                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            _raise_for(rc)
+        self._launch(C.c_void_p(x_hat.data_ptr()), C.c_void_p(nvar.data_ptr()), *ptrs, strides, B, C.c_void_p(out.data_ptr()))
         return out
-
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h:
-            self._lib.ce_demod_plan_destroy(h)

@@ -16,18 +16,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage
 
 _RANGES = {"slot": (0, 2 ** 31 - 1), "n_id": (0, 65535), "n_scid": (0, 1)}
-
-
-def _raise_for(code: int):
-    msg = _lib.last_error()
-    if code == _lib.CE_ERR_INVALID:
-        raise ValueError(msg)
-    if code == _lib.CE_ERR_UNSUPPORTED:
-        raise NotImplementedError(msg)
-    raise RuntimeError(f"libce_hip: {msg} (code {code})")
 
 
 def build_desc(hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, *, grid_start_crb: int = 0,
@@ -70,47 +61,28 @@ def build_desc(hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, *, g
 def derive_host(hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, *, grid_start_crb: int = 0,
                 n_symb_slot: int = 14) -> _lib.DmrsHostView:
     """Host-only view of what a plan holds (``ce_dmrs_derive_host``: jump tables, pilot lists); works without a GPU."""
-    lib = _lib.load()
     desc, keep = build_desc(hop1, hop2, n_layers, n_prb_grid, n_sym, grid_start_crb=grid_start_crb, n_symb_slot=n_symb_slot)
-    view = _lib.DmrsHostView()
-    rc = lib.ce_dmrs_derive_host(C.byref(desc), C.byref(view))
+    view = _stage.derive_host("ce_dmrs_derive_host", desc, _lib.DmrsHostView())
     del keep
-    if rc != 0:
-        _raise_for(rc)
     return view
 
 
-class PuschDmrs:
-    """Validated on construction (no GPU needed); the device plan is created at the first launch."""
+class PuschDmrs(_stage.Stage):
+    _CREATE, _DESTROY, _LAUNCH = "ce_dmrs_plan_create", "ce_dmrs_plan_destroy", "ce_dmrs_generate"
+    _NOUN = "the DM-RS generator"
 
     def __init__(self, hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, *, grid_start_crb: int = 0,
                  n_symb_slot: int = 14, device=None):
-        self._lib = _lib.load()
-        self._handle = None
+        super().__init__(device)
         self._geometry = (hop1, hop2, int(n_layers), int(n_prb_grid), int(n_sym))
         self._options = dict(grid_start_crb=int(grid_start_crb), n_symb_slot=int(n_symb_slot))
         view = derive_host(*self._geometry, **self._options)
         self.n_re, self.n_dmrs_total, self.n_layers = int(view.n_re), int(view.n_dmrs_total), int(n_layers)
-        self._device_arg = device
-        self.device: Optional[torch.device] = None
 
-    def _plan(self):
-        if self._handle is None:
-            device = self._device_arg
-            device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-            if device.type != "cuda":
-                raise RuntimeError("the DM-RS generator runs on a ROCm GPU only (no CPU fallback)")
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            desc, keep = build_desc(*self._geometry, device_index=device.index, **self._options)
-            handle = C.c_void_p()
-            with torch.cuda.device(device):
-                rc = self._lib.ce_dmrs_plan_create(C.byref(desc), C.byref(handle))
-            del keep
-            if rc != 0:
-                _raise_for(rc)
-            self._handle, self.device = handle, device
-        return self._handle
+    def _build_desc(self, device_index: int):
+        desc, keep = build_desc(*self._geometry, device_index=device_index, **self._options)
+        desc.keepalive = keep                                    # the PRB masks it points to live as long as the descriptor
+        return desc
 
     def _param(self, name: str, value):
         """-> (value, length or None for a scalar); host values are range-checked here, device tensors taken as they are."""
@@ -135,14 +107,13 @@ class PuschDmrs:
         B = max(lens) if lens else 1
         if any(n not in (1, B) for n in lens):
             raise ValueError(f"parameter lengths {lens} do not broadcast to one batch")
-        handle = self._plan()
+        self._plan()
         dev = self.device
         shape = (B, self.n_re, self.n_dmrs_total, self.n_layers)
         if out is None:
             out = torch.empty(shape, dtype=torch.complex64, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.complex64 or tuple(out.shape) != shape
-              or not out.is_contiguous() or out.device != dev):
-            raise ValueError(f"out must be a dense complex64 tensor of shape {shape} on {dev}")
+        else:
+            _stage.check_dense("out", out, torch.complex64, shape, dev, "complex64")
         if B == 0:
             return out                                           # empty batch: nothing to launch
         ptrs, strides = [], (C.c_int64 * 3)()
@@ -155,15 +126,6 @@ class PuschDmrs:
                 raise ValueError("negative strides are not supported")
             params[i] = (v, n)                                   # alive until the launch is enqueued (stream-ordered allocator)
             ptrs.append(C.c_void_p(v.data_ptr()))
-            strides[i] = 0 if v.shape[0] == 1 else int(v.stride(0))
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = self._lib.ce_dmrs_generate(handle, *ptrs, strides, B, C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            _raise_for(rc)
+            strides[i] = _stage.batch_stride(v)
+        self._launch(*ptrs, strides, B, C.c_void_p(out.data_ptr()))
         return out
-
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h:
-            self._lib.ce_dmrs_plan_destroy(h)

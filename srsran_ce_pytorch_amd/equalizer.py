@@ -17,8 +17,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from .dmrs import _raise_for
+from . import _lib, _stage
 
 CHUNK_SC = _lib.CE_EQ_CHUNK_SC      # subcarriers one workgroup of the kernel handles
 MAX_PORTS = _lib.CE_EQ_MAX_PORTS
@@ -55,29 +54,22 @@ def build_desc(hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, *, r
 
 def derive_host(hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, *, reserved_re_mask: int = 0xFFF) -> _lib.EqHostView:
     """Host-only view of what a plan holds (``ce_eq_derive_host``); works without a GPU."""
-    lib = _lib.load()
     desc = build_desc(hop1, hop2, n_layers, n_prb_grid, n_sym, reserved_re_mask=reserved_re_mask)
-    view = _lib.EqHostView()
-    rc = lib.ce_eq_derive_host(C.byref(desc), C.byref(view))
-    if rc != 0:
-        _raise_for(rc)
-    return view
+    return _stage.derive_host("ce_eq_derive_host", desc, _lib.EqHostView())
 
 
-class PuschEqualizer:
-    """Validated on construction (no GPU needed); the device plan is created at the first launch."""
+class PuschEqualizer(_stage.Stage):
+    _CREATE, _DESTROY, _LAUNCH = "ce_eq_plan_create", "ce_eq_plan_destroy", "ce_eq_equalize"
+    _NOUN = "the equalizer"
 
     def __init__(self, hop1, hop2, n_layers: int, n_prb_grid: int, n_sym: int = 14, reserved_re_mask: int = 0xFFF, device=None):
-        self._lib = _lib.load()
-        self._handle = None
+        super().__init__(device)
         self._geometry = (hop1, hop2, int(n_layers), int(n_prb_grid), int(n_sym))
         self._mask = int(reserved_re_mask)
         self._desc = build_desc(*self._geometry, reserved_re_mask=self._mask)
         self._view = derive_host(*self._geometry, reserved_re_mask=self._mask)
         self.n_data_re, self.n_layers = int(self._view.n_data_re), int(n_layers)
         self.n_sc, self.n_sym = 12 * int(n_prb_grid), int(n_sym)
-        self._device_arg = device
-        self.device: Optional[torch.device] = None
 
     def data_re(self) -> np.ndarray:
         """``(n_data_re, 2)`` int array: the ``(sym, sc)`` of every output row, from the plan's host view."""
@@ -93,22 +85,8 @@ class PuschEqualizer:
                         out[row] = (s, 12 * q + re)
         return out
 
-    def _plan(self):
-        if self._handle is None:
-            device = self._device_arg
-            device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-            if device.type != "cuda":
-                raise RuntimeError("the equalizer runs on a ROCm GPU only (no CPU fallback)")
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            desc = build_desc(*self._geometry, reserved_re_mask=self._mask, device_index=device.index)
-            handle = C.c_void_p()
-            with torch.cuda.device(device):
-                rc = self._lib.ce_eq_plan_create(C.byref(desc), C.byref(handle))
-            if rc != 0:
-                _raise_for(rc)
-            self._handle, self.device = handle, device
-        return self._handle
+    def _build_desc(self, device_index: int):
+        return build_desc(*self._geometry, reserved_re_mask=self._mask, device_index=device_index)
 
     def __call__(self, rx: torch.Tensor, ch_est: torch.Tensor, noise: torch.Tensor,
                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -116,7 +94,7 @@ class PuschEqualizer:
         ``[B, R, n_sc, n_sym]`` complex64 with any non-negative strides, ``ch_est`` the dense ``[B, R, n_sc, n_sym, L]``
         complex64 tensor and ``noise`` the dense ``[B, R]`` float64 tensor ``estimate()`` returns; ``out`` may pass the
         two result tensors to be overwritten."""
-        handle = self._plan()
+        self._plan()
         dev = self.device
         for name, t in (("rx", rx), ("ch_est", ch_est), ("noise", noise)):
             if not isinstance(t, torch.Tensor) or t.device != dev:
@@ -139,25 +117,12 @@ class PuschEqualizer:
         if out is None:
             out = (torch.empty(shape, dtype=torch.complex64, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
         x_hat, nvar = out
-        for name, t, dt in (("out[0]", x_hat, torch.complex64), ("out[1]", nvar, torch.float32)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{name} must be a dense {dt} tensor of shape {shape} on {dev}")
+        _stage.check_dense("out[0]", x_hat, torch.complex64, shape, dev)
+        _stage.check_dense("out[1]", nvar, torch.float32, shape, dev)
         if B == 0:
             return x_hat, nvar                                   # empty batch: nothing to launch
-        for name, t in (("ch_est", ch_est), ("out[0]", x_hat), ("out[1]", nvar)):
-            if t.data_ptr() % 16:
-                raise ValueError(f"{name} must be 16-byte aligned")
+        _stage.check_aligned(("ch_est", ch_est), ("out[0]", x_hat), ("out[1]", nvar))
         strides = (C.c_int64 * 4)(*[int(s) for s in rx.stride()])
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = self._lib.ce_eq_equalize(handle, C.c_void_p(rx.data_ptr()), strides, C.c_void_p(ch_est.data_ptr()),
-                                          C.c_void_p(noise.data_ptr()), B, R, C.c_void_p(x_hat.data_ptr()),
-                                          C.c_void_p(nvar.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            _raise_for(rc)
+        self._launch(C.c_void_p(rx.data_ptr()), strides, C.c_void_p(ch_est.data_ptr()), C.c_void_p(noise.data_ptr()), B, R,
+                     C.c_void_p(x_hat.data_ptr()), C.c_void_p(nvar.data_ptr()))
         return x_hat, nvar
-
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h:
-            self._lib.ce_eq_plan_destroy(h)

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._stage import raise_for
 
 
 def _np(x, dtype=None) -> np.ndarray:
@@ -73,14 +74,7 @@ def _hop_fields(hop, n_cdm: int):
 
 
 def _raise_for(code: int):
-    msg = _lib.last_error()
-    if code == _lib.CE_ERR_INVALID:
-        if msg in ("Hops should not overlap.", "The DM-RS mask should be the same for the two hops."):
-            raise AssertionError(msg)                      # T:862, T:869
-        raise ValueError(msg)
-    if code == _lib.CE_ERR_UNSUPPORTED:
-        raise NotImplementedError(msg)
-    raise RuntimeError(f"libce_hip: {msg} (code {code})")
+    raise_for(code, assertions=("Hops should not overlap.", "The DM-RS mask should be the same for the two hops."))   # T:862, T:869
 
 
 def _resolve(hop1, hop2, config, beta_dmrs, n_layers: int, n_prb_grid: int, n_sym: int, interp: str):

@@ -14,12 +14,10 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage
 from .demod import modulation_order
-from .dmrs import _raise_for
 
 
 def select_base_graph(tbs: int, rate: float) -> int:
@@ -47,22 +45,17 @@ def build_desc(base_graph: int, tbs: int, modulation, n_layers: int, n_bits: int
 def derive_host(base_graph: int, tbs: int, modulation, n_layers: int, n_bits: int, dtype=torch.int8, n_ref: int = 0,
                 filler_llr: float = 127.0) -> _lib.RmHostView:
     """Host-only view of everything a plan derives (``ce_rm_derive_host``); works without a GPU."""
-    lib = _lib.load()
     desc = build_desc(base_graph, tbs, modulation, n_layers, n_bits, dtype, n_ref, filler_llr)
-    view = _lib.RmHostView()
-    rc = lib.ce_rm_derive_host(C.byref(desc), C.byref(view))
-    if rc != 0:
-        _raise_for(rc)
-    return view
+    return _stage.derive_host("ce_rm_derive_host", desc, _lib.RmHostView())
 
 
-class PuschRateRecovery:
-    """Validated on construction (no GPU needed); the device plan is created at the first launch."""
+class PuschRateRecovery(_stage.Stage):
+    _CREATE, _DESTROY, _LAUNCH = "ce_rm_plan_create", "ce_rm_plan_destroy", "ce_rm_recover"
+    _NOUN = "rate recovery"
 
     def __init__(self, base_graph: int, tbs: int, modulation, n_layers: int, n_bits: int, dtype=torch.int8, n_ref: int = 0,
                  filler_llr: float = 127.0, device=None):
-        self._lib = _lib.load()
-        self._handle = None
+        super().__init__(device)
         self._args = (int(base_graph), int(tbs), modulation, int(n_layers), int(n_bits), dtype, int(n_ref), float(filler_llr))
         view = derive_host(*self._args)
         self.base_graph, self.tbs, self.qm, self.n_layers, self.n_bits = int(base_graph), int(tbs), modulation_order(modulation), int(n_layers), int(n_bits)
@@ -71,48 +64,16 @@ class PuschRateRecovery:
         self.e = [int(view.e_lo)] * int(view.n_lo) + [int(view.e_hi)] * (int(view.c) - int(view.n_lo))
         self.filler_range = (int(view.f0), int(view.f1))
         self.k0 = tuple(int(k) for k in view.k0)
-        self._device_arg = device
-        self.device: Optional[torch.device] = None
 
-    def _plan(self):
-        if self._handle is None:
-            device = self._device_arg
-            device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-            if device.type != "cuda":
-                raise RuntimeError("rate recovery runs on a ROCm GPU only (no CPU fallback)")
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            desc = build_desc(*self._args, device_index=device.index)
-            handle = C.c_void_p()
-            with torch.cuda.device(device):
-                rc = self._lib.ce_rm_plan_create(C.byref(desc), C.byref(handle))
-            if rc != 0:
-                _raise_for(rc)
-            self._handle, self.device = handle, device
-        return self._handle
-
-    def _rv(self, rv, B: int) -> torch.Tensor:
-        """-> an int32 device tensor of 1 or B elements; a host int is range-checked, a device tensor taken as it is
-        (the kernel uses ``rv & 3``)."""
-        dev = self.device
-        if isinstance(rv, torch.Tensor):
-            if rv.dtype != torch.int32 or rv.dim() != 1 or rv.shape[0] != B or rv.device != dev:
-                raise ValueError(f"rv: a tensor must be int32 of shape [{B}] on {dev}, got {rv.dtype} {tuple(rv.shape)} on {rv.device}")
-            if rv.stride(0) < 0:
-                raise ValueError("negative strides are not supported")
-            return rv
-        if isinstance(rv, bool) or not isinstance(rv, (int, np.integer)):
-            raise ValueError(f"rv: expected an int 0..3 or an int32 device tensor of shape [{B}]")
-        if not 0 <= int(rv) <= 3:
-            raise ValueError(f"rv={int(rv)} outside 0..3")
-        return torch.tensor([int(rv)], dtype=torch.int32).to(dev)      # on the current stream, like the launch that reads it
+    def _build_desc(self, device_index: int):
+        return build_desc(*self._args, device_index=device_index)
 
     def __call__(self, llr: torch.Tensor, rv, harq: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``soft[B, C, N_cb]`` (the plan's dtype) on the current stream.  ``llr`` is the dense ``[B, n_bits]`` row of the
         demapper; ``rv`` a Python int 0..3 for the whole batch or an int32 device tensor of length ``B``; ``harq`` the
         buffer kept from the earlier transmissions (``None`` = all zero); ``out`` may pass the result tensor to be
         overwritten, and may be ``harq`` itself."""
-        handle = self._plan()
+        self._plan()
         dev = self.device
         if not isinstance(llr, torch.Tensor) or llr.device != dev:
             raise ValueError(f"llr must be a tensor on {dev}")
@@ -120,31 +81,16 @@ class PuschRateRecovery:
             raise ValueError(f"llr must be a dense {self.dtype} tensor [slots, {self.n_bits}], got {llr.dtype} {tuple(llr.shape)}")
         B = llr.shape[0]
         shape = (B, self.n_code_blocks, self.n_cb)
-        if harq is not None and (not isinstance(harq, torch.Tensor) or harq.dtype != self.dtype or tuple(harq.shape) != shape
-                                 or not harq.is_contiguous() or harq.device != dev):
-            raise ValueError(f"harq must be a dense {self.dtype} tensor of shape {shape} on {dev}")
+        if harq is not None:
+            _stage.check_dense("harq", harq, self.dtype, shape, dev)
         if out is None:
             out = torch.empty(shape, dtype=self.dtype, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != self.dtype or tuple(out.shape) != shape
-              or not out.is_contiguous() or out.device != dev):
-            raise ValueError(f"out must be a dense {self.dtype} tensor of shape {shape} on {dev}")
-        rv_t = self._rv(rv, B)
+        else:
+            _stage.check_dense("out", out, self.dtype, shape, dev)
+        rv_t = _stage.batch_param("rv", rv, B, dev, 0, 3, "an int 0..3")   # (the kernel uses ``rv & 3`` of a device tensor)
         if B == 0:
             return out                                           # empty batch: nothing to launch
-        for name, t in (("llr", llr), ("harq", harq), ("out", out)):
-            if t is not None and t.data_ptr() % 16:
-                raise ValueError(f"{name} must be 16-byte aligned")
-        stride = 0 if rv_t.shape[0] == 1 else int(rv_t.stride(0))
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = self._lib.ce_rm_recover(handle, C.c_void_p(llr.data_ptr()), C.c_void_p(rv_t.data_ptr()), stride, B,
-                                         C.c_void_p(harq.data_ptr()) if harq is not None else None, C.c_void_p(out.data_ptr()),
-                                         C.c_void_p(stream))
-        if rc != 0:
-            _raise_for(rc)
+        _stage.check_aligned(("llr", llr), ("harq", harq), ("out", out))
+        self._launch(C.c_void_p(llr.data_ptr()), C.c_void_p(rv_t.data_ptr()), _stage.batch_stride(rv_t), B,
+                     C.c_void_p(harq.data_ptr()) if harq is not None else None, C.c_void_p(out.data_ptr()))
         return out
-
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h:
-            self._lib.ce_rm_plan_destroy(h)

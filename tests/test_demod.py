@@ -127,6 +127,38 @@ def test_host_tables_combine_to_the_bit_serial_sequence(lib, c):
         assert np.array_equal(_combine(x1, jump, ci, G), D.scrambling(ci, G)), hex(ci)
 
 
+def test_dmrs_and_descrambling_tables_sample_one_generator(lib):
+    """The DM-RS rows and the demapper's jump entries are the one generator of csrc/ce_gold.h sampled two ways: row T[i]
+    holds the x2-only words of c for c_init = 1 << i, a jump entry the 31-bit x2 state at a block's first bit -- the low
+    31 bits of that block's first word; the x1 words are the same words."""
+    from srsran_ce_pytorch_amd import dmrs
+    h1, h2, _ = S.numpy_hops(S.bench_case("filter", 1))
+    view = dmrs.derive_host(h1, h2, 1, 273, 14)                          # full band from CRB 0: words 0 .. 102
+    assert (view.word0[0], view.n_words[0]) == (0, 103)
+    x1, jump = DM.gold_tables(2, 1664)
+    bw = _lib.CE_DEMOD_BLOCK_WORDS
+    assert x1.shape == (104,) and jump.shape == (13, 31) and bw * 12 < 103
+    assert np.array_equal(x1[:103], np.array(view.x1[0][:103], np.uint32))
+    t = np.array([view.t[0][i][:103] for i in range(31)], np.uint32)     # [i][word]
+    assert np.array_equal(jump.T, t[:, ::bw] & np.uint32(0x7FFFFFFF))    # jump[blk, i] == T[i][8 blk] & 0x7FFFFFFF
+
+
+def test_signature_tables_cover_every_entry_point(lib):
+    """Every exported entry point carries the restype and argtypes of its table, one argtype per declared parameter."""
+    tables = {"ce_hip.h": (_lib.EXPORTS, _lib.SIGNATURES), "ce_denoise.h": (_lib.EXPORTS_DENOISE, _lib.SIGNATURES_DENOISE),
+              "ce_dmrs.h": (_lib.EXPORTS_DMRS, _lib.SIGNATURES_DMRS), "ce_eq.h": (_lib.EXPORTS_EQ, _lib.SIGNATURES_EQ),
+              "ce_demod.h": (_lib.EXPORTS_DEMOD, _lib.SIGNATURES_DEMOD), "ce_rm.h": (_lib.EXPORTS_RM, _lib.SIGNATURES_RM)}
+    assert sorted(tables) == sorted(_lib.PUBLIC_HEADERS)
+    for header, (exports, table) in tables.items():
+        declared = dict(re.findall(r"\b(ce_\w+)\s*\(([^()]*)\)\s*;", (ROOT / "include" / header).read_text()))
+        assert exports == list(table) and set(exports) <= set(declared), header
+        for name in exports:
+            fn, (restype, argtypes) = getattr(lib, name), table[name]
+            assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype is restype, name
+            params = declared[name].strip()
+            assert len(argtypes) == (0 if params in ("", "void") else params.count(",") + 1), name
+
+
 def test_table_bytes_stay_under_half_of_the_slot_traffic(lib):
     """Qm = 8, int8: a slot reads 12 M bytes and writes 8 M; its workgroups read the x1 words once and 31 jump entries
     per block: M + 124 M / 32 bytes -- under half of 20 M.  A full 31-row table over all words would be 32 M."""

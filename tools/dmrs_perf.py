@@ -10,17 +10,14 @@ DM-RS symbols [2, 11], 8192 slots, L = 1 and L = 4.  Three timings alternate in 
 and, for scale, the estimation step the pilots feed (headline workload: 4 Rx, RC filter, L = 1) in the same run.
 Writes means and spread, (a)/(b) and (c)/(a) to profiles/dmrs_perf.txt (--out).  `--rehearse` runs the host-side logic on
 a few slots without a GPU and measures nothing."""
-import argparse
 import statistics
-import sys
 import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT)]
-import numpy as np  # noqa: E402
+import numpy as np
 
-from srsran_ce_pytorch_amd import dmrs, synth as S  # noqa: E402
+from _perf_common import finish, gpu, parser, stats, timed
+
+from srsran_ce_pytorch_amd import dmrs, synth as S
 
 
 def host_pilots(view, n_layers, slots, n_ids, n_scids, n_symb_slot=14):
@@ -46,19 +43,11 @@ def host_pilots(view, n_layers, slots, n_ids, n_scids, n_symb_slot=14):
     return out.view(np.float32).view(np.complex64)[..., 0]
 
 
-def stats(xs):
-    return f"mean {statistics.mean(xs):9.4f} ms  min {min(xs):9.4f}  max {max(xs):9.4f}  (n={len(xs)})"
-
-
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = parser(__doc__, "dmrs_perf", rehearse_help="host logic only, on 4 slots; no GPU, nothing measured, nothing written")
     ap.add_argument("--slots", type=int, default=8192)
-    ap.add_argument("--launches", type=int, default=20, help="launches per repeat of the device timings (>= 20)")
-    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--layers", type=int, nargs="+", default=[1, 4])
     ap.add_argument("--no-estimate", action="store_true", help="skip the estimation step (12 GB of received grids at 8192 slots)")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "dmrs_perf.txt"))
-    ap.add_argument("--rehearse", action="store_true", help="host logic only, on 4 slots; no GPU, nothing measured, nothing written")
     args = ap.parse_args()
 
     rng = np.random.default_rng(1)
@@ -75,19 +64,7 @@ def main():
 
     import torch
     from srsran_ce_pytorch_amd import estimator as E
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/dmrs_perf.py measures on a GPU; none is visible (use --rehearse for the host logic)")
-    dev = torch.device("cuda:0")
-    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
-
-    def timed(fn, n):
-        e0, e1 = ev(), ev()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / n
+    dev = gpu("dmrs_perf")
 
     for L in args.layers:
         case = S.bench_case("filter", L)
@@ -127,22 +104,19 @@ def main():
                 ts.append(timed(step, args.launches))
         ma, mb, mc = (statistics.mean(x) for x in (ta, tb, tc[1:]))
         lines += [f"L={L}: {nbytes / 1e6:.1f} MB per step ({nbytes // B} B per slot)",
-                  f"  (a) PuschDmrs kernel, per-slot device parameters   {stats(ta)}   {nbytes / ma / 1e6:8.1f} GB/s",
-                  f"  (b) device fill of the same bytes                  {stats(tb)}   {nbytes / mb / 1e6:8.1f} GB/s",
-                  f"  (c) numpy on the host + copy to the device         {stats(tc[1:])}   (first, untimed-for-mean run: {ms_c0:.1f} ms)",
+                  f"  (a) PuschDmrs kernel, per-slot device parameters   {stats(ta, 9)}   {nbytes / ma / 1e6:8.1f} GB/s",
+                  f"  (b) device fill of the same bytes                  {stats(tb, 9)}   {nbytes / mb / 1e6:8.1f} GB/s",
+                  f"  (c) numpy on the host + copy to the device         {stats(tc[1:], 9)}   (first, untimed-for-mean run: {ms_c0:.1f} ms)",
                   f"  (a)/(b) = {ma / mb:.3f}    (c)/(a) = {mc / ma:.1f}"]
         if ts:
             ms = statistics.mean(ts)
-            lines += [f"  estimation step fed by these pilots (4 Rx, RC filter)  {stats(ts)}",
+            lines += [f"  estimation step fed by these pilots (4 Rx, RC filter)  {stats(ts, 9)}",
                       f"  (a) / estimation step = {ma / ms:.4f}    (c) / estimation step = {mc / ms:.2f}"]
         del out, fill, staged
         if step:
             del rx, est_out, step
         torch.cuda.empty_cache()
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(text)
+    finish(lines, args.out)
 
 
 if __name__ == "__main__":

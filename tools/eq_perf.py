@@ -8,31 +8,19 @@ symbols [2, 11], 4 Rx, L = 1 at 8192 slots and L = 4 at 2048 slots.  Two timings
 (a) reads the data REs only (12 of the 14 symbols with the default reserved_re_mask) and writes x_hat and nvar; (b) reads
 every byte of both tensors and writes two scalars.  Writes means and spread, (a)/(b) and the TB/s each implies on its own
 bytes to profiles/eq_perf.txt (--out).  `--rehearse` runs the host-side logic without a GPU and measures nothing."""
-import argparse
 import statistics
-import sys
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT)]
+from _perf_common import finish, gpu, parser, stats, timed
 
-from srsran_ce_pytorch_amd import equalizer as EQ, synth as S  # noqa: E402
+from srsran_ce_pytorch_amd import equalizer as EQ, synth as S
 
 SHAPES = [(1, 8192), (4, 2048)]     # (layers, slots)
 PORTS = 4
 
 
-def stats(xs):
-    return f"mean {statistics.mean(xs):9.4f} ms  min {min(xs):9.4f}  max {max(xs):9.4f}  (n={len(xs)})"
-
-
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--launches", type=int, default=20, help="launches per repeat of the device timings (>= 20)")
-    ap.add_argument("--repeats", type=int, default=5)
+    ap = parser(__doc__, "eq_perf")
     ap.add_argument("--slots-scale", type=float, default=1.0, help="scale both batch sizes (a smaller card)")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "eq_perf.txt"))
-    ap.add_argument("--rehearse", action="store_true", help="host logic only; no GPU, nothing measured, nothing written")
     args = ap.parse_args()
 
     lines = [f"tools/eq_perf.py: 273 PRB, DM-RS [2, 11], {PORTS} Rx; {args.launches} launches x {args.repeats} repeats, alternating (a) (b)"]
@@ -44,19 +32,7 @@ def main():
         return
 
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/eq_perf.py measures on a GPU; none is visible (use --rehearse for the host logic)")
-    dev = torch.device("cuda:0")
-    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
-
-    def timed(fn, n):
-        e0, e1 = ev(), ev()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / n
+    dev = gpu("eq_perf")
 
     g = torch.Generator(device=dev)
     g.manual_seed(7)
@@ -87,15 +63,12 @@ def main():
             tb.append(timed(b, args.launches))
         ma, mb = statistics.mean(ta), statistics.mean(tb)
         lines += [f"L={L}, {B} slots: ch_est {ch.numel() * 8 / 1e9:.2f} GB, rx {rx_buf.numel() * 8 / 1e9:.2f} GB, x_hat + nvar {B * eq.n_data_re * L * 12 / 1e9:.2f} GB",
-                  f"  (a) PuschEqualizer, one launch                     {stats(ta)}   {bytes_a / ma / 1e9:6.2f} TB/s on {bytes_a / 1e9:.2f} GB (data REs in, results out)",
-                  f"  (b) torch.sum over both tensors' float32 views     {stats(tb)}   {bytes_b / mb / 1e9:6.2f} TB/s on {bytes_b / 1e9:.2f} GB (every byte in)",
+                  f"  (a) PuschEqualizer, one launch                     {stats(ta, 9)}   {bytes_a / ma / 1e9:6.2f} TB/s on {bytes_a / 1e9:.2f} GB (data REs in, results out)",
+                  f"  (b) torch.sum over both tensors' float32 views     {stats(tb, 9)}   {bytes_b / mb / 1e9:6.2f} TB/s on {bytes_b / 1e9:.2f} GB (every byte in)",
                   f"  (a)/(b) = {ma / mb:.3f}"]
         del rx_buf, rx, ch, out, rx_f, ch_f
         torch.cuda.empty_cache()
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(text)
+    finish(lines, args.out)
 
 
 if __name__ == "__main__":

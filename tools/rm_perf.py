@@ -10,24 +10,16 @@ tool prints A, the base graph and the resulting C.  Two timings alternate in one
 
 (b) reads and writes the same total as (a) reads and writes.  Writes means and spread, (a)/(b) and the TB/s each implies on
 its own bytes to profiles/rm_perf.txt (--out).  `--rehearse` runs the host-side logic without a GPU and measures nothing."""
-import argparse
 import statistics
-import sys
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path[:0] = [str(ROOT)]
+import torch
 
-import torch  # noqa: E402
+from _perf_common import finish, gpu, parser, stats, timed
 
-from srsran_ce_pytorch_amd import ratematch as RM  # noqa: E402
+from srsran_ce_pytorch_amd import ratematch as RM
 
 SLOTS, M, BG, LAYERS = 8192, 273 * 12 * 12, 1, 1
 CONFIGS = [(qm, fmt, harq) for qm in (2, 8) for fmt in (torch.float32, torch.int8) for harq in (False, True)]
-
-
-def stats(xs):
-    return f"mean {statistics.mean(xs):8.4f} ms  min {min(xs):8.4f}  max {max(xs):8.4f}  (n={len(xs)})"
 
 
 def choose_tbs(qm):
@@ -44,12 +36,8 @@ def choose_tbs(qm):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--launches", type=int, default=20, help="launches per repeat of the device timings (>= 20)")
-    ap.add_argument("--repeats", type=int, default=5)
+    ap = parser(__doc__, "rm_perf")
     ap.add_argument("--slots-scale", type=float, default=1.0, help="scale the batch size (a smaller card)")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "rm_perf.txt"))
-    ap.add_argument("--rehearse", action="store_true", help="host logic only; no GPU, nothing measured, nothing written")
     args = ap.parse_args()
     B = max(1, int(SLOTS * args.slots_scale))
 
@@ -67,19 +55,7 @@ def main():
             print(f"Qm={qm} {fmt} harq={harq}: {v.n_tiles} workgroups per slot of {v.unit_elems} element(s) per 4-byte unit -- not measured")
         return
 
-    if not torch.cuda.is_available():
-        raise SystemExit("tools/rm_perf.py measures on a GPU; none is visible (use --rehearse for the host logic)")
-    dev = torch.device("cuda:0")
-    ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
-
-    def timed(fn, n):
-        e0, e1 = ev(), ev()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / n
+    dev = gpu("rm_perf")
 
     g = torch.Generator(device=dev)
     g.manual_seed(7)
@@ -118,10 +94,7 @@ def main():
                   f"  (a)/(b) = {ma / mb:.3f}   (per repeat {min(p / q for p, q in zip(ta, tb)):.3f} .. {max(p / q for p, q in zip(ta, tb)):.3f})"]
         del rm, llr, harq, out, src, dst
         torch.cuda.empty_cache()
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(text)
+    finish(lines, args.out)
 
 
 if __name__ == "__main__":
