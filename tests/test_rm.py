@@ -192,23 +192,20 @@ def _divmod_f32(a, d):
     return q, m
 
 
-@pytest.mark.parametrize("unit", [1, 4], ids=["f32", "i8"])
-@pytest.mark.parametrize("c", R.CASES, ids=IDS)
-def test_kernel_gather_arithmetic_against_the_literal_walk(lib, c, unit):
-    """The closed form of include/ce_rm.h exactly as csrc/ce_rm.hip evaluates it -- the buffers of three slots cut at the
-    4-byte grid of the output into units of 1 (float32) or 4 (int8) elements, (k, j, i) divided out once per unit and
-    stepped from element to element, a second hit divided again -- under every rv: each source index lies inside the
-    block's part of the row and belongs to that position in the oracle's map, every position of a buffer is visited by
-    exactly one unit, and every element of the row is read exactly once."""
-    d = R.case_derive(c)
-    v = _lib_derive(c, torch.int8 if unit == 4 else torch.float32)
+def check_gather_arithmetic(d, v, unit, slots, rvs=range(4)):
+    """The closed form of include/ce_rm.h exactly as csrc/ce_rm.hip evaluates it -- the buffers of the slots `slots` cut at
+    the 4-byte grid of the output into units of 1 (float32) or 4 (int8) elements, (k, j, i) divided out once per unit and
+    stepped from element to element, a second hit divided again -- under every rv of `rvs`: each source index lies inside
+    the block's part of the row and belongs to that position in the oracle's map, every position of a buffer is visited
+    by exactly one unit, and every element of the row is read exactly once.  `d` is the oracle's derivation, `v` the
+    library's host view of the same descriptor in the format of `unit`."""
     qm, nf = d.qm, d.f1 - d.f0
     assert v.unit_elems == unit
-    for rv in range(4):
+    for rv in rvs:
         blk, pos, kk = R.slot_map(d, rv)
         s = int(v.s[rv])
         assert s == (d.k0[rv] if d.k0[rv] < d.f0 else d.f0 if d.k0[rv] < d.f1 else d.k0[rv] - nf)
-        for b in range(R.N_SLOTS):
+        for b in slots:
             seen = np.zeros(d.G, np.int64)
             for r in range(d.C):
                 e_r = v.e_lo if r < v.n_lo else v.e_hi
@@ -256,6 +253,13 @@ def test_kernel_gather_arithmetic_against_the_literal_walk(lib, c, unit):
                     k, i, j = np.where(wrap, 0, k), np.where(wrap, 0, i), np.where(wrap, 0, j)
                 assert np.all(visited == 1)
             assert np.all(seen == 1)
+
+
+@pytest.mark.parametrize("unit", [1, 4], ids=["f32", "i8"])
+@pytest.mark.parametrize("c", R.CASES, ids=IDS)
+def test_kernel_gather_arithmetic_against_the_literal_walk(lib, c, unit):
+    """check_gather_arithmetic over every index of every case: three slots, every rv, both formats."""
+    check_gather_arithmetic(R.case_derive(c), _lib_derive(c, torch.int8 if unit == 4 else torch.float32), unit, range(R.N_SLOTS))
 
 
 def test_reciprocal_division_is_exact_below_2_pow_21():
