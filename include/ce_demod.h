@@ -10,7 +10,7 @@
  * fastest); nvar, float32, the same shape (the complex noise variance of each symbol, 1 / SINR).
  * Modulation order Qm in {2, 4, 6, 8}: QPSK, 16QAM, 64QAM, 256QAM with the Gray maps of TS 38.211 5.1.3 - 5.1.6, e.g.
  *     16QAM   d = ((1 - 2 b0)(2 - (1 - 2 b2)) + j (1 - 2 b1)(2 - (1 - 2 b3))) / sqrt(10)
- * pi/2-BPSK, transform precoding and UCI placeholder bits are out of scope.
+ * pi/2-BPSK and UCI placeholder bits are out of scope; transform precoding is undone before this stage (ce_tp.h).
  *
  * LLR of bit j of symbol i (y = x_hat_i, the minima over the constellation points s with that bit value):
  *     llr(i Qm + j) = (min_{s: b_j(s) = 1} |y - s|^2  -  min_{s: b_j(s) = 0} |y - s|^2) / nvar_i

@@ -1,0 +1,112 @@
+/*
+ * ce_tp.h -- EXTENSION of libce_hip.so with NO counterpart in the reference: transform de-precoding (DFT-s-OFDM, the
+ * inverse of TS 38.211 6.3.1.4) between ce_eq_equalize and ce_demod_demap, with the per-RE noise variances combined
+ * into the per-symbol one the demapper needs.
+ *
+ * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
+ * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
+ * tolerance rules stated there.
+ *
+ * Transform precoding is single-layer and is used with DM-RS symbols that carry no data, so the equalizer's output
+ * of such a slot is S = n_symbols rows of exactly M = 12 n_prbs entries: x_hat[slot][S M] complex64 and nvar[slot][S M]
+ * float32, symbol ascending, subcarrier ascending (with intra-slot hopping both hops have the same n_prbs).  For one
+ * layer the equalizer's x_hat_k = z / g is a per-RE zero-forcing estimate with nvar_k = 1 / g; a plain IDFT of it would
+ * let one faded RE's noise flood the symbol and a single nvar_k = +inf erase it.  The operator is the MMSE
+ * frequency-domain equalizer's combination, recovered from (x_hat, nvar) alone.  Per row (slot b, data symbol s),
+ * k, i = 0 .. M - 1:
+ *     usable_k = nvar_k finite and > 0, and both parts of x_hat_k finite
+ *     beta_k   = 1 / (1 + nvar_k)        if usable_k, else 0     (the LMMSE weight g / (1 + g))
+ *     gamma_k  = nvar_k / (1 + nvar_k)   if usable_k, else 1     (= 1 - beta_k, without the cancellation)
+ *     u_k      = beta_k x_hat_k          if usable_k, else 0     (selected, never multiplied: no 0 * inf)
+ *     mu       = (1 / M) sum_k beta_k
+ *     t_i      = (1 / sqrt(M)) sum_k u_k exp(+j 2 pi i k / M)
+ *     x_out_i    = t_i / mu
+ *     nvar_out_i = (sum_k gamma_k) / (sum_k beta_k), the same value for every i of the row
+ *     where sum_k beta_k = 0 (no usable RE):  x_out_i = 0, nvar_out_i = +inf   (the demapper's erasure convention)
+ * x_out is unbiased (the coefficient of the transmitted x_i in t_i is mu); the residual inter-symbol interference plus
+ * noise has variance mu (1 - mu) for unit-power symbols, hence nvar_out = (1 - mu) / mu.
+ *
+ * nvar_out is written broadcast over the row ([slot][S M] float32, the shape of x_out), so that ce_demod_demap consumes
+ * both outputs unchanged: 4 M bytes written per row where 4 would do, a sixth of the pass's 24 M bytes per row.
+ *
+ * float32 arithmetic of the kernel (restated in tests/tp_oracle.py `deprecode_f32`): the two sums are taken in a fixed
+ * order (threads_per_row partial sums, thread t over the REs 4 g .. 4 g + 3 of the groups g = t, t + threads_per_row,
+ * .. in ascending order, then a balanced tree), so a row's result does not depend on the batch or on the row's place
+ * in it; the transform is a Stockham mixed-radix FFT over the radix sequence of the host view with the twiddles
+ * W[n] = exp(+j 2 pi n / M) computed on the host in float64 and rounded once; the output scale is sqrt(M) / sum_k beta_k.
+ */
+#ifndef CE_TP_H
+#define CE_TP_H
+
+#include "ce_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define CE_TP_MAX_PRBS 275
+#define CE_TP_MAX_PASSES 8 /* the longest radix sequence has 7 entries (e.g. M = 3240: 4 2 3 3 3 3 5) */
+
+typedef struct ce_tp_desc {
+  int32_t abi_version; /* = CE_ABI_VERSION */
+  int32_t device;      /* HIP device ordinal the plan lives on */
+  int32_t n_prbs;      /* 1 .. 275 of the form 2^a 3^b 5^c (38.211 6.3.1.4): M = 12 n_prbs */
+  int32_t n_symbols;   /* S: data symbols per slot, 1 .. 14 */
+} ce_tp_desc;
+
+typedef struct ce_tp_plan ce_tp_plan; /* opaque */
+
+typedef struct ce_tp_info {
+  int32_t m_sc;           /* M */
+  int32_t n_symbols;      /* S */
+  int64_t bytes_per_slot; /* S M 24: x_hat and nvar in, x_out and nvar_out out */
+} ce_tp_info;
+
+/* What ce_tp_plan_create derives on the host. */
+typedef struct ce_tp_host_view {
+  int32_t m_sc;                         /* M */
+  int32_t n_passes;                     /* entries of `radix` */
+  int32_t radix[CE_TP_MAX_PASSES];      /* from {4, 2, 3, 5}, in pass order; their product is M */
+  uint32_t stride_magic[CE_TP_MAX_PASSES]; /* pass p works at stride s_p = radix[0] .. radix[p-1]: floor(2^32 / s_p) + 1,
+                                           so that floor(i / s_p) = (i * magic) >> 32 for i < M; 0 where s_p = 1 */
+  int32_t threads_per_row;              /* 64, 128 or 256 */
+  int32_t rows_per_workgroup;           /* 4, 2 or 1: threads_per_row * rows_per_workgroup = threads */
+  int32_t threads;                      /* 256 */
+  int32_t lds_bytes;                    /* rows_per_workgroup * 2 * 8 M: ping-pong buffers */
+  int32_t twiddle_bytes;                /* 8 M */
+  int32_t n_workgroups_per_slot;        /* ceil(S / rows_per_workgroup): a workgroup never spans two slots */
+} ce_tp_host_view;
+
+/* Validation and derivation of ce_tp_plan_create without touching a GPU: usable on a CPU-only host.
+ * CE_ERR_INVALID: n_prbs outside 1..275 or with a prime factor above 5; n_symbols outside 1..14. */
+int ce_tp_derive_host(const ce_tp_desc* desc, ce_tp_host_view* view);
+
+/* Host only: the plan's twiddle table W[n] = exp(+j 2 pi n / M), n < M, as M (re, im) float32 pairs into `twiddles`
+ * (twiddle_bytes of the host view). */
+int ce_tp_copy_twiddles(const ce_tp_desc* desc, float* twiddles);
+
+/* Validates the descriptor and uploads the twiddle table. */
+int ce_tp_plan_create(const ce_tp_desc* desc, ce_tp_plan** out);
+void ce_tp_plan_destroy(ce_tp_plan* plan);
+int ce_tp_plan_get_info(const ce_tp_plan* plan, ce_tp_info* info);
+
+/*
+ * De-precoding of n_slots slots in ONE launch on `stream` (a hipStream_t; NULL = the default stream).  Asynchronous;
+ * n_slots == 0 launches nothing.
+ *  x_hat     [slot][S M] complex64, dense (ce_eq_equalize's x_hat of a one-layer slot)
+ *  nvar      [slot][S M] float32, dense
+ *  x_out     [slot][S M] complex64, dense; may be x_hat itself
+ *  nvar_out  [slot][S M] float32, dense; may be nvar itself
+ * In place is safe because a workgroup reads all of its rows before it writes any of them and no other workgroup
+ * touches them; any other overlap between inputs and outputs is undefined.  All four pointers must be 16-byte aligned
+ * (CE_ERR_INVALID otherwise); every row then is too, since 8 M and 4 M are multiples of 16, and every access to
+ * the four tensors is 16 bytes wide.  No atomics, no scratch; every address comes from the block index, the thread index and
+ * host-derived plan values, tensor values enter arithmetic only.
+ */
+int ce_tp_deprecode(const ce_tp_plan* plan, const void* x_hat, const float* nvar, int64_t n_slots, void* x_out, float* nvar_out,
+                    void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CE_TP_H */

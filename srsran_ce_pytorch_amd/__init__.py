@@ -1,3 +1,4 @@
 """MI355X-native PUSCH DM-RS channel estimator (batched, HIP kernels behind a C ABI)."""
 from .config import EstimatorConfig, HopConfig, empty_hop  # noqa: F401
+from .deprecode import PuschTransformDeprecoder  # noqa: F401
 from .ratematch import PuschRateRecovery, select_base_graph  # noqa: F401

@@ -21,10 +21,11 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_stage.h", "ce_gold.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 PUBLIC_HEADERS = ["ce_hip.h", "ce_denoise.h", "ce_dmrs.h", "ce_eq.h", "ce_demod.h", "ce_rm.h"]   # include/
+PUBLIC_HEADERS_TP = ["ce_tp.h"]   # include/: the transform de-precoder's, with SIGNATURES_TP below
 
 CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
@@ -219,6 +220,33 @@ SIGNATURES_RM = {                                                               
     "ce_rm_recover": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
 }
 EXPORTS_RM = list(SIGNATURES_RM)
+CE_TP_MAX_PRBS, CE_TP_MAX_PASSES = 275, 8
+
+
+class TpDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("n_prbs", C.c_int32), ("n_symbols", C.c_int32)]
+
+
+class TpInfo(C.Structure):
+    _fields_ = [("m_sc", C.c_int32), ("n_symbols", C.c_int32), ("bytes_per_slot", C.c_int64)]
+
+
+class TpHostView(C.Structure):
+    _fields_ = [("m_sc", C.c_int32), ("n_passes", C.c_int32), ("radix", C.c_int32 * CE_TP_MAX_PASSES),
+                ("stride_magic", C.c_uint32 * CE_TP_MAX_PASSES), ("threads_per_row", C.c_int32),
+                ("rows_per_workgroup", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32),
+                ("twiddle_bytes", C.c_int32), ("n_workgroups_per_slot", C.c_int32)]
+
+
+SIGNATURES_TP = {                                                                         # include/ce_tp.h (extension)
+    "ce_tp_derive_host": (_int, [_P(TpDesc), _P(TpHostView)]),
+    "ce_tp_copy_twiddles": (_int, [_P(TpDesc), _vp]),
+    "ce_tp_plan_create": (_int, [_P(TpDesc), _P(_vp)]),
+    "ce_tp_plan_destroy": (None, [_vp]),
+    "ce_tp_plan_get_info": (_int, [_vp, _P(TpInfo)]),
+    "ce_tp_deprecode": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+}
+EXPORTS_TP = list(SIGNATURES_TP)
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -247,7 +275,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS] + [Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP] + [Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -302,7 +330,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the estimator has no CPU fallback)")
     lib = C.CDLL(str(LIB_PATH))
-    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM):
+    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -1,0 +1,352 @@
+// EXTENSION (no reference counterpart, see include/ce_tp.h): transform de-precoding -- per data symbol the MMSE-weighted
+// inverse DFT of length M = 12 n_prbs of the equalizer's x_hat, and the per-symbol noise variance the demapper needs.
+//
+// Kernel: one 256-thread workgroup handles rows_per_workgroup rows (data symbols) of one slot, threads_per_row = 64, 128
+// or 256 threads each (whole waves, so everything that depends on the row is wave-uniform); a row lives in two
+// LDS buffers of M complex64 from the load to the store.
+//   load   thread t of the row takes the groups g = t, t + threads_per_row, .. of 4 REs (two 16-byte loads of x_hat,
+//          one of nvar), forms u_k, beta_k, gamma_k, adds beta and gamma to its own two partial sums in ascending k and
+//          writes u into buffer 0 in natural order.  The partial sums are reduced by a butterfly of lane exchanges
+//          inside the wave (offsets 32 .. 1: a balanced tree, every lane ends with the same bits) and, for rows of two or
+//          four waves, (w0 + w1) + (w2 + w3) through LDS: the longest addition chain is
+//          4 ceil(M / 4 / threads_per_row) + log2(threads_per_row), and nothing depends on the batch.
+//   passes Stockham autosort, decimation in frequency, radix sequence r_0 r_1 .. from the host: at stride s (the product
+//          of the radices before) butterfly i < M / r reads src[i + k M / r], k < r, takes the r-point inverse DFT,
+//          multiplies output j by W[p j s] with p = floor(i / s) (one table of M twiddles for every pass, since the
+//          pass's own root of unity is W^s; p j s < M) and writes dst[(i - p s) + s (r p + j)].  The reads are contiguous
+//          over the lanes; the division is one v_mul_hi with a host-derived constant.  One barrier per pass.  The last
+//          pass has p = 0 (no twiddles), applies sqrt(M) / sum beta and leaves the row in natural order.
+//   store  16-byte stores of the row from LDS and of the broadcast nvar_out, contiguous over the lanes.
+// In place is safe: the stores come after the last barrier, the loads before the first.  DESIGN 6i.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <memory>
+#include <vector>
+
+#include "ce_stage.h"
+#include "ce_tp.h"
+
+namespace {
+
+constexpr int TP_NT = 256;
+
+struct TpDev {
+  uint32_t m;            // M
+  uint32_t n_sym;        // S
+  uint32_t tpr_log2;     // log2(threads_per_row)
+  uint32_t rpw;          // rows per workgroup
+  uint32_t wg_per_slot;  // workgroups per slot
+  uint32_t n_passes;
+  uint32_t radix[CE_TP_MAX_PASSES];
+  uint32_t magic[CE_TP_MAX_PASSES];
+  float sqrt_m;          // float32(sqrt(M))
+};
+
+__device__ __forceinline__ float2 operator+(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 operator-(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 operator*(float c, float2 a) { return make_float2(c * a.x, c * a.y); }
+__device__ __forceinline__ float2 tp_cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
+// a + j b and a - j b
+__device__ __forceinline__ float2 tp_add_j(float2 a, float2 b) { return make_float2(a.x - b.y, a.y + b.x); }
+__device__ __forceinline__ float2 tp_sub_j(float2 a, float2 b) { return make_float2(a.x + b.y, a.y - b.x); }
+
+// y_j = sum_k x_k exp(+j 2 pi j k / R)
+template <int R>
+__device__ __forceinline__ void tp_butterfly(const float2 (&x)[R], float2 (&y)[R]) {
+  if constexpr (R == 2) {
+    y[0] = x[0] + x[1];
+    y[1] = x[0] - x[1];
+  } else if constexpr (R == 4) {
+    const float2 t0 = x[0] + x[2], t1 = x[0] - x[2], t2 = x[1] + x[3], t3 = x[1] - x[3];
+    y[0] = t0 + t2;
+    y[1] = tp_add_j(t1, t3);
+    y[2] = t0 - t2;
+    y[3] = tp_sub_j(t1, t3);
+  } else if constexpr (R == 3) {
+    const float2 t = x[1] + x[2], u = x[1] - x[2];
+    const float2 m = x[0] - 0.5f * t, v = 0.8660254037844386f * u;
+    y[0] = x[0] + t;
+    y[1] = tp_add_j(m, v);
+    y[2] = tp_sub_j(m, v);
+  } else {
+    static_assert(R == 5, "radices 2, 3, 4 and 5");
+    constexpr float c1 = 0.30901699437494745f, c2 = -0.8090169943749475f, s1 = 0.9510565162951535f, s2 = 0.5877852522924731f;
+    const float2 t1 = x[1] + x[4], t2 = x[2] + x[3], u1 = x[1] - x[4], u2 = x[2] - x[3];
+    const float2 m1 = (x[0] + c1 * t1) + c2 * t2, m2 = (x[0] + c2 * t1) + c1 * t2;
+    const float2 n1 = s1 * u1 + s2 * u2, n2 = s2 * u1 - s1 * u2;
+    y[0] = (x[0] + t1) + t2;
+    y[1] = tp_add_j(m1, n1);
+    y[2] = tp_add_j(m2, n2);
+    y[3] = tp_sub_j(m2, n2);
+    y[4] = tp_sub_j(m1, n1);
+  }
+}
+
+// One pass over one row: `nb` = M / R butterflies at stride `s`; magic = floor(2^32 / s) + 1, or 0 where s = 1.
+template <int R, bool LAST>
+__device__ __forceinline__ void tp_pass(const float2* src, float2* dst, const float2* __restrict__ tw, uint32_t nb, uint32_t s, uint32_t magic,
+                                        uint32_t lane, uint32_t tpr, float scale) {
+  for (uint32_t i = lane; i < nb; i += tpr) {
+    float2 x[R], y[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) x[k] = src[i + k * nb];
+    tp_butterfly<R>(x, y);
+    if constexpr (LAST) {   // s = nb, p = 0: no twiddles, natural order
+#pragma unroll
+      for (int j = 0; j < R; ++j) dst[i + j * nb] = scale * y[j];
+    } else {
+      const uint32_t p = magic ? __umulhi(i, magic) : i;   // floor(i / s)
+      const uint32_t ps = p * s;
+      const uint32_t o = (i - ps) + ps * R;
+      dst[o] = y[0];
+#pragma unroll
+      for (int j = 1; j < R; ++j) dst[o + s * j] = tp_cmul(y[j], tw[ps * j]);
+    }
+  }
+}
+
+template <bool LAST>
+__device__ __forceinline__ void tp_pass_any(uint32_t r, const float2* src, float2* dst, const float2* __restrict__ tw, uint32_t nb, uint32_t s,
+                                            uint32_t magic, uint32_t lane, uint32_t tpr, float scale) {
+  switch (r) {   // uniform
+    case 4: tp_pass<4, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
+    case 2: tp_pass<2, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
+    case 3: tp_pass<3, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
+    default: tp_pass<5, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
+  }
+}
+
+// beta, gamma and u of one RE (include/ce_tp.h); an unusable RE is selected away, never multiplied
+__device__ __forceinline__ float2 tp_weigh(float xr, float xi, float nv, float& sb, float& sg) {
+  const bool ok = nv > 0.0f && nv < INFINITY && fabsf(xr) < INFINITY && fabsf(xi) < INFINITY;   // a NaN fails its comparison
+  const float d = 1.0f + nv;
+  const float beta = ok ? 1.0f / d : 0.0f;
+  const float gamma = ok ? nv / d : 1.0f;
+  sb += beta;
+  sg += gamma;
+  return make_float2(ok ? beta * xr : 0.0f, ok ? beta * xi : 0.0f);
+}
+
+__global__ __launch_bounds__(TP_NT) void ce_tp_kernel(TpDev P, const float2* __restrict__ tw, const float4* x_in, const float4* nv_in, float4* x_out,
+                                                      float4* nv_out) {
+  // x_in / x_out and nv_in / nv_out may be the same buffers: no __restrict__; every load of the workgroup's rows comes
+  // before the first barrier, every store after the last
+  extern __shared__ float4 tp_lds[];
+  __shared__ float red[TP_NT / 64][2];
+  const uint32_t M = P.m, tpr = 1u << P.tpr_log2;
+  const uint32_t slot = blockIdx.x / P.wg_per_slot, wg = blockIdx.x - slot * P.wg_per_slot;
+  const uint32_t rl = threadIdx.x >> P.tpr_log2, lane = threadIdx.x & (tpr - 1u);   // row of the workgroup (wave-uniform), thread of the row
+  const uint32_t row = wg * P.rpw + rl;
+  const bool active = row < P.n_sym;   // the slot's last workgroup may hold fewer rows
+  const int64_t grow = (int64_t)slot * P.n_sym + row;
+  float2* buf0 = reinterpret_cast<float2*>(tp_lds) + (size_t)rl * 2u * M;
+  float2* buf1 = buf0 + M;
+  const uint32_t n_grp = M >> 2;   // groups of 4 REs
+
+  // ---- load: u into buf0, the two sums ----
+  float sb = 0.0f, sg = 0.0f;
+  {
+    const float4* xr = x_in + grow * (int64_t)(M >> 1);
+    const float4* nr = nv_in + grow * (int64_t)n_grp;
+    float4* u4 = reinterpret_cast<float4*>(buf0);
+    for (uint32_t g = lane; g < n_grp; g += tpr) {
+      float4 nv = make_float4(-1.0f, -1.0f, -1.0f, -1.0f), xa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), xb = xa;
+      if (active) {
+        nv = nr[g];
+        xa = xr[2u * g];
+        xb = xr[2u * g + 1u];
+      }
+      const float2 u0 = tp_weigh(xa.x, xa.y, nv.x, sb, sg);
+      const float2 u1 = tp_weigh(xa.z, xa.w, nv.y, sb, sg);
+      const float2 u2 = tp_weigh(xb.x, xb.y, nv.z, sb, sg);
+      const float2 u3 = tp_weigh(xb.z, xb.w, nv.w, sb, sg);
+      u4[2u * g] = make_float4(u0.x, u0.y, u1.x, u1.y);
+      u4[2u * g + 1u] = make_float4(u2.x, u2.y, u3.x, u3.y);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {   // a + b = b + a: both partners of an exchange get the same bits
+    sb += __shfl_xor(sb, off);
+    sg += __shfl_xor(sg, off);
+  }
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0u) {
+    red[wave][0] = sb;
+    red[wave][1] = sg;
+  }
+  __syncthreads();
+  if (P.tpr_log2 == 7u) {
+    const uint32_t w0 = wave & ~1u;
+    sb = red[w0][0] + red[w0 + 1u][0];
+    sg = red[w0][1] + red[w0 + 1u][1];
+  } else if (P.tpr_log2 == 8u) {
+    sb = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    sg = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+  }
+  const bool any = sb > 0.0f;
+  const float scale = any ? P.sqrt_m / sb : 0.0f;        // 1 / (sqrt(M) mu)
+  const float nvo = any ? sg / sb : INFINITY;
+
+  // ---- passes ----
+  float2* src = buf0;
+  float2* dst = buf1;
+  uint32_t s = 1u;
+  for (uint32_t pass = 0; pass + 1u < P.n_passes; ++pass) {
+    const uint32_t r = P.radix[pass];
+    tp_pass_any<false>(r, src, dst, tw, M / r, s, P.magic[pass], lane, tpr, 1.0f);
+    s *= r;
+    __syncthreads();
+    float2* t = src;
+    src = dst;
+    dst = t;
+  }
+  {
+    const uint32_t r = P.radix[P.n_passes - 1u];
+    tp_pass_any<true>(r, src, dst, tw, s, s, 0u, lane, tpr, scale);   // M / r = s: the last radix closes the product
+    __syncthreads();
+  }
+
+  // ---- store ----
+  if (active) {
+    const float4* res = reinterpret_cast<const float4*>(dst);
+    float4* xo = x_out + grow * (int64_t)(M >> 1);
+    float4* no = nv_out + grow * (int64_t)n_grp;
+    for (uint32_t h = lane; h < (M >> 1); h += tpr) xo[h] = res[h];
+    const float4 nv4 = make_float4(nvo, nvo, nvo, nvo);
+    for (uint32_t g = lane; g < n_grp; g += tpr) no[g] = nv4;
+  }
+}
+
+// ---- host derivation ----
+
+int tp_derive(const ce_tp_desc* d, ce_tp_host_view* v) {
+  memset(v, 0, sizeof(*v));
+  if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
+  if (d->n_prbs < 1 || d->n_prbs > CE_TP_MAX_PRBS) return ce_fail(CE_ERR_INVALID, "n_prbs=%d outside 1..%d", d->n_prbs, CE_TP_MAX_PRBS);
+  if (d->n_symbols < 1 || d->n_symbols > CE_MAX_SYMBOLS) return ce_fail(CE_ERR_INVALID, "n_symbols=%d outside 1..%d", d->n_symbols, CE_MAX_SYMBOLS);
+  int rest = d->n_prbs, e[3] = {2, 1, 0};   // exponents of 2, 3, 5 in M = 12 n_prbs
+  const int primes[3] = {2, 3, 5};
+  for (int i = 0; i < 3; ++i)
+    while (rest % primes[i] == 0) {
+      rest /= primes[i];
+      ++e[i];
+    }
+  if (rest != 1) return ce_fail(CE_ERR_INVALID, "n_prbs=%d has a prime factor above 5: transform precoding allocates 2^a 3^b 5^c PRBs", d->n_prbs);
+  const int M = 12 * d->n_prbs;
+  int n = 0;
+  for (int i = 0; i < e[0] / 2; ++i) v->radix[n++] = 4;
+  if (e[0] & 1) v->radix[n++] = 2;
+  for (int i = 0; i < e[1]; ++i) v->radix[n++] = 3;
+  for (int i = 0; i < e[2]; ++i) v->radix[n++] = 5;   // at most 7 entries for M <= 3300
+  v->n_passes = n;
+  uint32_t s = 1;
+  for (int i = 0; i < n; ++i) {
+    v->stride_magic[i] = s == 1 ? 0u : (uint32_t)(0x100000000ull / s) + 1u;   // exact for i s < 2^32 (i < M <= 3300, s <= M)
+    s *= (uint32_t)v->radix[i];
+  }
+  v->m_sc = M;
+  // a row's threads: about one radix-4 butterfly each in the small rows, where lanes would idle otherwise
+  v->threads_per_row = M <= 384 ? 64 : M <= 1152 ? 128 : 256;
+  v->threads = TP_NT;
+  v->rows_per_workgroup = TP_NT / v->threads_per_row;
+  v->lds_bytes = v->rows_per_workgroup * 2 * 8 * M;
+  v->twiddle_bytes = 8 * M;
+  v->n_workgroups_per_slot = (d->n_symbols + v->rows_per_workgroup - 1) / v->rows_per_workgroup;
+  return CE_OK;
+}
+
+void tp_twiddles(int M, float* out) {
+  const double two_pi = 6.283185307179586476925286766559;
+  for (int n = 0; n < M; ++n) {
+    const double a = two_pi * (double)n / (double)M;
+    out[2 * n] = (float)cos(a);
+    out[2 * n + 1] = (float)sin(a);
+  }
+}
+
+}  // namespace
+
+struct ce_tp_plan {
+  int device = 0;
+  ce_tp_info info{};
+  TpDev dev{};
+  int lds_bytes = 0;
+  float2* tw = nullptr;
+};
+
+extern "C" int ce_tp_derive_host(const ce_tp_desc* d, ce_tp_host_view* v) {
+  if (!d || !v) return ce_fail(CE_ERR_INVALID, "null argument");
+  return tp_derive(d, v);
+}
+
+extern "C" int ce_tp_copy_twiddles(const ce_tp_desc* d, float* twiddles) {
+  if (!d || !twiddles) return ce_fail(CE_ERR_INVALID, "null argument");
+  ce_tp_host_view v;
+  if (const int rc = tp_derive(d, &v); rc != CE_OK) return rc;
+  tp_twiddles(v.m_sc, twiddles);
+  return CE_OK;
+}
+
+extern "C" int ce_tp_plan_create(const ce_tp_desc* d, ce_tp_plan** out) {
+  if (!d || !out) return ce_fail(CE_ERR_INVALID, "null argument");
+  ce_tp_host_view v;
+  if (const int rc = tp_derive(d, &v); rc != CE_OK) return rc;
+  auto p = ce_new_plan<ce_tp_plan>();
+  if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
+  p->device = d->device;
+  p->info.m_sc = v.m_sc;
+  p->info.n_symbols = d->n_symbols;
+  p->info.bytes_per_slot = (int64_t)d->n_symbols * v.m_sc * 24;
+  p->lds_bytes = v.lds_bytes;
+  TpDev& D = p->dev;
+  D.m = (uint32_t)v.m_sc;
+  D.n_sym = (uint32_t)d->n_symbols;
+  D.tpr_log2 = v.threads_per_row == 64 ? 6u : v.threads_per_row == 128 ? 7u : 8u;
+  D.rpw = (uint32_t)v.rows_per_workgroup;
+  D.wg_per_slot = (uint32_t)v.n_workgroups_per_slot;
+  D.n_passes = (uint32_t)v.n_passes;
+  for (int i = 0; i < CE_TP_MAX_PASSES; ++i) {
+    D.radix[i] = (uint32_t)v.radix[i];
+    D.magic[i] = v.stride_magic[i];
+  }
+  D.sqrt_m = (float)sqrt((double)v.m_sc);
+  std::vector<float> tw(2 * (size_t)v.m_sc);
+  tp_twiddles(v.m_sc, tw.data());
+  CeDeviceScope scope(d->device);
+  const hipError_t e = ce_upload(scope.err, &p->tw, tw.data(), tw.size() * sizeof(float));
+  if (e != hipSuccess) {
+    ce_tp_plan_destroy(p.release());
+    return ce_fail(CE_ERR_HIP, "de-precoder plan upload: %s", hipGetErrorString(e));
+  }
+  *out = p.release();
+  return CE_OK;
+}
+
+extern "C" void ce_tp_plan_destroy(ce_tp_plan* p) {
+  if (!p) return;
+  if (p->tw) (void)hipFree(p->tw);
+  delete p;
+}
+
+extern "C" int ce_tp_plan_get_info(const ce_tp_plan* p, ce_tp_info* info) { return ce_get_info(p, info); }
+
+extern "C" int ce_tp_deprecode(const ce_tp_plan* p, const void* x_hat, const float* nvar, int64_t n_slots, void* x_out, float* nvar_out,
+                               void* stream) {
+  if (!p) return ce_fail(CE_ERR_INVALID, "null argument");
+  if (n_slots < 0) return ce_fail(CE_ERR_INVALID, "n_slots=%lld", (long long)n_slots);
+  if (n_slots == 0) return CE_OK;
+  if (!x_hat || !nvar || !x_out || !nvar_out) return ce_fail(CE_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(x_hat) | reinterpret_cast<uintptr_t>(nvar) | reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(nvar_out)) & 15u)
+    return ce_fail(CE_ERR_INVALID, "x_hat, nvar, x_out and nvar_out must be 16-byte aligned");
+  const int64_t n_wg = n_slots * (int64_t)p->dev.wg_per_slot;
+  if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.wg_per_slot);
+  CeDeviceScope scope(p->device);
+  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
+  hipLaunchKernelGGL(ce_tp_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->lds_bytes, (hipStream_t)stream, p->dev, p->tw,
+                     reinterpret_cast<const float4*>(x_hat), reinterpret_cast<const float4*>(nvar), reinterpret_cast<float4*>(x_out),
+                     reinterpret_cast<float4*>(nvar_out));
+  return ce_launch_status("transform de-precoding");
+}

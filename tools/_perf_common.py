@@ -1,4 +1,4 @@
-"""What the stage perf tools (dmrs_perf.py, eq_perf.py, demod_perf.py, rm_perf.py) share: the common arguments, the device
+"""What the stage perf tools (dmrs_perf.py, eq_perf.py, demod_perf.py, rm_perf.py, tp_perf.py) share: the common arguments, the device
 check, the event timing of LAUNCHES launches, the spread line, and the print-and-write tail.  Each tool keeps its own
 shapes, its (a)/(b)/(c) definitions and its line formats."""
 import argparse
