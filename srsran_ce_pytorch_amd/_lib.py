@@ -21,11 +21,12 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ldpc.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_stage.h", "ce_gold.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 PUBLIC_HEADERS = ["ce_hip.h", "ce_denoise.h", "ce_dmrs.h", "ce_eq.h", "ce_demod.h", "ce_rm.h"]   # include/
 PUBLIC_HEADERS_TP = ["ce_tp.h"]   # include/: the transform de-precoder's, with SIGNATURES_TP below
+PUBLIC_HEADERS_LDPC = ["ce_ldpc.h"]   # include/: the LDPC decoder's, with SIGNATURES_LDPC below
 
 CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
@@ -247,6 +248,41 @@ SIGNATURES_TP = {                                                               
     "ce_tp_deprecode": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 EXPORTS_TP = list(SIGNATURES_TP)
+CE_LDPC_MAX_ZC, CE_LDPC_MAX_ROWS, CE_LDPC_MAX_COLS, CE_LDPC_MAX_ROW_DEGREE = 384, 46, 68, 19
+CE_LDPC_L_BOUND, CE_LDPC_LDS_MAX, CE_LDPC_F32, CE_LDPC_I8 = 4497, 163840, 0, 1
+CE_LDPC_STATE_IDX_SHIFT, CE_LDPC_STATE_MAG_SHIFT = 19, 24
+_i32p = C.POINTER(C.c_int32)
+
+
+class LdpcDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("zc", C.c_int32), ("n_rows", C.c_int32), ("n_cols", C.c_int32),
+                ("n_punctured_cols", C.c_int32), ("n_in", C.c_int32), ("k_out", C.c_int32), ("in_format", C.c_int32),
+                ("max_iters", C.c_int32), ("early_stop", C.c_int32), ("llr_scale", C.c_float),
+                ("row_start", _i32p), ("col", _i32p), ("shift", _i32p)]
+
+
+class LdpcInfo(C.Structure):
+    _fields_ = [("n_edges", C.c_int32), ("row_bytes", C.c_int32), ("n_bits", C.c_int32), ("blocks_per_workgroup", C.c_int32),
+                ("threads", C.c_int32), ("lds_bytes", C.c_int32)]
+
+
+class LdpcHostView(C.Structure):
+    _fields_ = [("n_sys", C.c_int32), ("n_edges", C.c_int32), ("max_row_degree", C.c_int32), ("max_col_degree", C.c_int32),
+                ("row_bytes", C.c_int32), ("n_bits", C.c_int32), ("threads_per_block", C.c_int32),
+                ("blocks_per_workgroup", C.c_int32), ("threads", C.c_int32), ("lds_l_bytes", C.c_int32),
+                ("lds_state32_bytes", C.c_int32), ("lds_state8_bytes", C.c_int32), ("lds_bytes_per_block", C.c_int32),
+                ("lds_flag_bytes", C.c_int32), ("lds_bytes", C.c_int32), ("schedule_bytes", C.c_int32),
+                ("state_idx_shift", C.c_int32), ("state_mag_shift", C.c_int32)]
+
+
+SIGNATURES_LDPC = {                                                                       # include/ce_ldpc.h (extension)
+    "ce_ldpc_derive_host": (_int, [_P(LdpcDesc), _P(LdpcHostView)]),
+    "ce_ldpc_plan_create": (_int, [_P(LdpcDesc), _P(_vp)]),
+    "ce_ldpc_plan_destroy": (None, [_vp]),
+    "ce_ldpc_plan_get_info": (_int, [_vp, _P(LdpcInfo)]),
+    "ce_ldpc_decode": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+}
+EXPORTS_LDPC = list(SIGNATURES_LDPC)
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -275,7 +311,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP] + [Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP + PUBLIC_HEADERS_LDPC] + [Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -330,7 +366,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the estimator has no CPU fallback)")
     lib = C.CDLL(str(LIB_PATH))
-    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP):
+    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP, SIGNATURES_LDPC):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

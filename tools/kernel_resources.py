@@ -35,13 +35,17 @@ def short(name):
     if m:
         return "<L%s,NH%s,ND%s,KPT%s,F%s>" % m.groups()
     m = re.search(r"ce_narrow_kernelILi(\d)ELi(\d)E", name)
-    return "narrow<L%s,NH%s>" % m.groups() if m else name[:40]
+    if m:
+        return "narrow<L%s,NH%s>" % m.groups()
+    m = re.search(r"\d+(ce_[a-z0-9_]+_kernel)E", name)      # a stage's kernel in an anonymous namespace
+    return m.group(1) if m else name[:40]
 
 
 if __name__ == "__main__":
     flags = [a for a in sys.argv[1:] if a.startswith("-")]
     only = [a for a in sys.argv[1:] if not a.startswith("-")]
-    srcs = [s for s in sorted(CSRC.glob("ce_inst_*.hip")) if not only or any(o in s.name for o in only)]
+    # the estimation kernels' units by default; a stage's own unit (ce_ldpc, ce_tp, ...) when it is named
+    srcs = [s for s in sorted(CSRC.glob("ce_*.hip")) if any(o in s.name for o in only) or (not only and s.name.startswith("ce_inst_"))]
     sys.path.insert(0, str(ROOT))
     from srsran_ce_pytorch_amd._lib import EXTRA_FLAGS   # each unit with its own flags, as the build applies them
     with ThreadPoolExecutor(8) as pool:
