@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "ce_rm.h"
+#include "ce_segment.h"
 #include "ce_stage.h"
 
 namespace {
@@ -204,18 +205,9 @@ int rm_derive(const ce_rm_desc* d, ce_rm_host_view* v) {
   if (d->format == CE_RM_F32 && !(d->filler_llr > 0.0f && d->filler_llr < INFINITY)) return ce_fail(CE_ERR_INVALID, "filler_llr=%g must be positive and finite", (double)d->filler_llr);
   if (d->n_ref < 0) return ce_fail(CE_ERR_INVALID, "n_ref=%d is negative", d->n_ref);
   const bool bg1 = d->base_graph == 1;
-  const int64_t A = d->tbs, B = A + (A > 3824 ? 24 : 16), K_cb = bg1 ? 8448 : 3840;
-  const int64_t C = B <= K_cb ? 1 : (B + K_cb - 25) / (K_cb - 24);
-  const int64_t Bp = C == 1 ? B : B + 24 * C;
-  if (B % C != 0) return ce_fail(CE_ERR_INVALID, "tbs=%d: B=%lld is no multiple of C=%lld code blocks", d->tbs, (long long)B, (long long)C);
-  const int64_t Kp = Bp / C;
-  const int64_t K_b = bg1 ? 22 : B > 640 ? 10 : B > 560 ? 9 : B > 192 ? 8 : 6;
-  if (Kp > K_b * 384) return ce_fail(CE_ERR_INVALID, "K'=%lld exceeds K_b * 384 = %lld", (long long)Kp, (long long)(K_b * 384));
-  int64_t Zc = 0;
-  for (int a : {2, 3, 5, 7, 9, 11, 13, 15})
-    for (int64_t z = a; z <= 384; z *= 2)
-      if (K_b * z >= Kp && (Zc == 0 || z < Zc)) Zc = z;
-  const int64_t K = (bg1 ? 22 : 10) * Zc, N = (bg1 ? 66 : 50) * Zc;
+  CeSegment seg;   // 5.2.2 and the lifting size: shared with ce_tb
+  if (const int rc = ce_segment_derive(d->base_graph, d->tbs, &seg); rc != CE_OK) return rc;
+  const int64_t B = seg.b, K_cb = seg.k_cb, C = seg.c, Bp = seg.b_prime, Kp = seg.k_prime, K_b = seg.k_b, Zc = seg.zc, K = seg.k, N = seg.n;
   if (d->n_ref != 0 && d->n_ref < K - 2 * Zc) return ce_fail(CE_ERR_INVALID, "n_ref=%d is below K - 2 Zc = %lld", d->n_ref, (long long)(K - 2 * Zc));
   const int64_t N_cb = d->n_ref == 0 ? N : (N < d->n_ref ? N : (int64_t)d->n_ref);
   const int64_t f0 = Kp - 2 * Zc, f1 = K - 2 * Zc, P = N_cb - (f1 - f0);
