@@ -21,13 +21,14 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_stage.h", "ce_segment.h", "ce_gold.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 PUBLIC_HEADERS = ["ce_hip.h", "ce_denoise.h", "ce_dmrs.h", "ce_eq.h", "ce_demod.h", "ce_rm.h"]   # include/
 PUBLIC_HEADERS_TP = ["ce_tp.h"]   # include/: the transform de-precoder's, with SIGNATURES_TP below
 PUBLIC_HEADERS_LDPC = ["ce_ldpc.h"]   # include/: the LDPC decoder's, with SIGNATURES_LDPC below
 PUBLIC_HEADERS_TB = ["ce_tb.h"]   # include/: transport-block assembly's, with SIGNATURES_TB below
+PUBLIC_HEADERS_ENC = ["ce_enc.h"]   # include/: the transport-block encoder's, with SIGNATURES_ENC below
 
 CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
@@ -312,6 +313,40 @@ SIGNATURES_TB = {                                                               
     "ce_tb_assemble": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 EXPORTS_TB = list(SIGNATURES_TB)
+CE_ENC_THREADS, CE_ENC_CORE_TRIANGULAR, CE_ENC_CORE_NR, CE_ENC_CRC_CHUNK = 256, 0, 1, 1024
+
+
+class EncDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("base_graph", C.c_int32), ("tbs", C.c_int32), ("qm", C.c_int32),
+                ("n_layers", C.c_int32), ("g_bits", C.c_int32), ("n_ref", C.c_int32), ("n_rows", C.c_int32), ("n_cols", C.c_int32),
+                ("row_start", _i32p), ("col", _i32p), ("shift", _i32p)]
+
+
+class EncInfo(C.Structure):
+    _fields_ = [("n_code_blocks", C.c_int32), ("tb_row_bytes", C.c_int32), ("g_row_bytes", C.c_int32), ("cw_row_bytes", C.c_int32),
+                ("cw_required", C.c_int32), ("reserved0", C.c_int32), ("bytes_per_slot", C.c_int64)]
+
+
+class EncHostView(C.Structure):
+    _fields_ = [("b", C.c_int32), ("k_cb", C.c_int32), ("c", C.c_int32), ("b_prime", C.c_int32), ("k_prime", C.c_int32),
+                ("k_b", C.c_int32), ("zc", C.c_int32), ("k", C.c_int32), ("n", C.c_int32), ("n_cb", C.c_int32),
+                ("f0", C.c_int32), ("f1", C.c_int32), ("p_rm", C.c_int32), ("n_lo", C.c_int32), ("e_lo", C.c_int32),
+                ("e_hi", C.c_int32), ("k0", C.c_int32 * 4), ("s", C.c_int32 * 4), ("l_tb", C.c_int32), ("l_cb", C.c_int32),
+                ("p", C.c_int32), ("g_tb", C.c_int32), ("g_cb", C.c_int32), ("tb_row_bytes", C.c_int32), ("g_row_bytes", C.c_int32),
+                ("cw_row_bytes", C.c_int32), ("n_sys", C.c_int32), ("n_edges", C.c_int32), ("core_form", C.c_int32),
+                ("core_rows", C.c_int32), ("core_shift", C.c_int32), ("rows_needed", C.c_int32), ("col_dwords", C.c_int32),
+                ("ext_dwords", C.c_int32), ("cw_required", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32),
+                ("table_bytes", C.c_int32)]
+
+
+SIGNATURES_ENC = {                                                                        # include/ce_enc.h (extension)
+    "ce_enc_derive_host": (_int, [_P(EncDesc), _P(EncHostView)]),
+    "ce_enc_plan_create": (_int, [_P(EncDesc), _P(_vp)]),
+    "ce_enc_plan_destroy": (None, [_vp]),
+    "ce_enc_plan_get_info": (_int, [_vp, _P(EncInfo)]),
+    "ce_enc_encode": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+}
+EXPORTS_ENC = list(SIGNATURES_ENC)
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -340,7 +375,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP + PUBLIC_HEADERS_LDPC + PUBLIC_HEADERS_TB] + [Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP + PUBLIC_HEADERS_LDPC + PUBLIC_HEADERS_TB + PUBLIC_HEADERS_ENC] + [Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -395,7 +430,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the estimator has no CPU fallback)")
     lib = C.CDLL(str(LIB_PATH))
-    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP, SIGNATURES_LDPC, SIGNATURES_TB):
+    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP, SIGNATURES_LDPC, SIGNATURES_TB, SIGNATURES_ENC):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
