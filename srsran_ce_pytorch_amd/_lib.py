@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 HEADERS = ["ce_plan.h", "ce_stage.h", "ce_segment.h", "ce_gold.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
 PUBLIC_HEADERS = ["ce_hip.h", "ce_denoise.h", "ce_dmrs.h", "ce_eq.h", "ce_demod.h", "ce_rm.h"]   # include/
@@ -29,6 +29,7 @@ PUBLIC_HEADERS_TP = ["ce_tp.h"]   # include/: the transform de-precoder's, with 
 PUBLIC_HEADERS_LDPC = ["ce_ldpc.h"]   # include/: the LDPC decoder's, with SIGNATURES_LDPC below
 PUBLIC_HEADERS_TB = ["ce_tb.h"]   # include/: transport-block assembly's, with SIGNATURES_TB below
 PUBLIC_HEADERS_ENC = ["ce_enc.h"]   # include/: the transport-block encoder's, with SIGNATURES_ENC below
+PUBLIC_HEADERS_MOD = ["ce_mod.h"]   # include/: the modulator's, with SIGNATURES_MOD below
 
 CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
@@ -347,6 +348,44 @@ SIGNATURES_ENC = {                                                              
     "ce_enc_encode": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
 }
 EXPORTS_ENC = list(SIGNATURES_ENC)
+CE_MAX_LAYERS, CE_MOD_THREADS, CE_MOD_TILE_SC, CE_MOD_GROUP_SYMBOLS, CE_MOD_MAX_TILE_BLOCKS = 4, 256, 256, 7, 34
+CE_MOD_A = {2: 0x3F3504F3, 4: 0x3EA1E89B, 6: 0x3E1E01B3, 8: 0x3D9D130E}   # float32 bit patterns of A_qm
+
+
+class ModHopDesc(C.Structure):
+    _fields_ = [("dmrs_symbols", C.c_uint8 * CE_MAX_SYMBOLS), ("re_mask", C.c_uint16 * CE_MAX_CDM), ("reserved_re_mask", C.c_uint16),
+                ("prb_start", C.c_int32), ("n_prbs", C.c_int32), ("start_symbol", C.c_int32), ("n_alloc_symbols", C.c_int32),
+                ("mask_prbs", C.POINTER(C.c_uint8))]
+
+
+class ModDesc(C.Structure):
+    _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("n_prb_grid", C.c_int32), ("n_sym", C.c_int32), ("n_layers", C.c_int32),
+                ("qm", C.c_int32), ("scramble", C.c_int32), ("n_hops", C.c_int32), ("hop", ModHopDesc * CE_MAX_HOPS)]
+
+
+class ModInfo(C.Structure):
+    _fields_ = [("n_bits", C.c_int32), ("n_symbols", C.c_int32), ("n_data_re", C.c_int32), ("g_row_bytes", C.c_int32), ("n_re", C.c_int32),
+                ("n_dmrs_total", C.c_int32), ("bytes_per_slot", C.c_int64)]
+
+
+class ModHostView(C.Structure):
+    _fields_ = [("n_bits", C.c_int32), ("g_row_bytes", C.c_int32), ("n_data_re", C.c_int32), ("n_symbols", C.c_int32), ("n_re", C.c_int32),
+                ("n_dmrs_total", C.c_int32), ("sym_hop", C.c_int32 * CE_MAX_SYMBOLS), ("data_mask", C.c_int32 * CE_MAX_SYMBOLS),
+                ("data_res_per_prb", C.c_int32 * CE_MAX_SYMBOLS), ("first_row", C.c_int32 * CE_MAX_SYMBOLS),
+                ("dmrs_col", C.c_int32 * CE_MAX_SYMBOLS), ("n_words", C.c_int32), ("block_words", C.c_int32), ("n_blocks", C.c_int32),
+                ("table_bytes", C.c_int32), ("tile_sc", C.c_int32), ("tiles_per_symbol", C.c_int32), ("group_symbols", C.c_int32), ("n_groups", C.c_int32),
+                ("workgroups_per_slot", C.c_int32),
+                ("max_tile_blocks", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32)]
+
+
+SIGNATURES_MOD = {                                                                        # include/ce_mod.h (extension)
+    "ce_mod_derive_host": (_int, [_P(ModDesc), _P(ModHostView)]),
+    "ce_mod_plan_create": (_int, [_P(ModDesc), _P(_vp)]),
+    "ce_mod_plan_destroy": (None, [_vp]),
+    "ce_mod_plan_get_info": (_int, [_vp, _P(ModInfo)]),
+    "ce_mod_modulate": (_int, [_vp, _vp, _vp, _i64, C.c_float, _vp, _vp, _i64p, _i64, _vp, _vp]),
+}
+EXPORTS_MOD = list(SIGNATURES_MOD)
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -375,7 +414,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP + PUBLIC_HEADERS_LDPC + PUBLIC_HEADERS_TB + PUBLIC_HEADERS_ENC] + [Path(__file__)]
+    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP + PUBLIC_HEADERS_LDPC + PUBLIC_HEADERS_TB + PUBLIC_HEADERS_ENC + PUBLIC_HEADERS_MOD] + [Path(__file__)]
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -430,7 +469,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the estimator has no CPU fallback)")
     lib = C.CDLL(str(LIB_PATH))
-    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP, SIGNATURES_LDPC, SIGNATURES_TB, SIGNATURES_ENC):
+    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP, SIGNATURES_LDPC, SIGNATURES_TB, SIGNATURES_ENC, SIGNATURES_MOD):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -276,17 +276,7 @@ int dq_derive(const ce_demod_desc* d, ce_demod_host_view* v) {
 
 // x1[n_blocks * DQ_BW] and jump[n_blocks][31]
 void dq_tables(const ce_demod_host_view& v, std::vector<uint32_t>& x1, std::vector<uint32_t>& jump) {
-  const size_t nb = (size_t)v.n_blocks, nw = nb * DQ_BW;
-  x1.assign(nw, 0u);
-  jump.assign(nb * 31, 0u);
-  if (nw) ce_gold_words<false>(1u, 0, (int)nw - 1, x1.data());   // x1(0) = 1, x1(1 .. 30) = 0
-  for (int i = 0; i < 31; ++i) {
-    uint32_t s = ce_gold_state_at<true>(1u << i, 0);
-    for (size_t blk = 0; blk < nb; ++blk) {
-      jump[blk * 31 + i] = s;
-      for (int k = 0; k < DQ_BW; ++k) (void)ce_gold_step_word<true>(s);
-    }
-  }
+  ce_gold_block_tables((size_t)v.n_blocks, DQ_BW, x1, jump);   // shared with the modulator (ce_gold.h)
 }
 
 }  // namespace

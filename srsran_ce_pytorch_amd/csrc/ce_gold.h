@@ -1,5 +1,6 @@
 // The Gold sequence of TS 38.211 5.2.1, c(n) = x1(n + Nc) ^ x2(n + Nc), a word (32 bits) at a time.  The one generator of
-// the DM-RS tables (ce_dmrs.hip), the descrambling tables and the demapper's kernel (ce_demod.hip); DESIGN 6d.
+// the DM-RS tables (ce_dmrs.hip), the (de)scrambling tables and the kernels of the demapper and the modulator (ce_demod.hip,
+// ce_mod.hip); DESIGN 6d.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,4 +34,22 @@ template <bool IS_X2>
 inline void ce_gold_words(uint32_t init, int w_lo, int w_hi, uint32_t* out) {
   uint32_t s = ce_gold_state_at<IS_X2>(init, w_lo);
   for (int w = w_lo; w <= w_hi; ++w) out[w - w_lo] = ce_gold_step_word<IS_X2>(s);
+}
+
+// Host: the tables of a scrambling sequence cut into blocks of `block_words` words (the demapper's and the modulator's;
+// ce_demod.h): x1[n_blocks * block_words], the words of c for c_init = 0, and jump[n_blocks][31], the 31-bit x2 state at each
+// block's first bit for c_init = 1 << i.
+template <class Vec>
+inline void ce_gold_block_tables(size_t n_blocks, int block_words, Vec& x1, Vec& jump) {
+  const size_t nw = n_blocks * (size_t)block_words;
+  x1.assign(nw, 0u);
+  jump.assign(n_blocks * 31, 0u);
+  if (nw) ce_gold_words<false>(1u, 0, (int)nw - 1, x1.data());   // x1(0) = 1, x1(1 .. 30) = 0
+  for (int i = 0; i < 31; ++i) {
+    uint32_t s = ce_gold_state_at<true>(1u << i, 0);
+    for (size_t blk = 0; blk < n_blocks; ++blk) {
+      jump[blk * 31 + i] = s;
+      for (int k = 0; k < block_words; ++k) (void)ce_gold_step_word<true>(s);
+    }
+  }
 }
