@@ -10,6 +10,7 @@ import os
 import shutil
 import subprocess
 from pathlib import Path
+from typing import NamedTuple
 
 PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
@@ -23,14 +24,23 @@ KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # units compile concurrently (ce_inst.inc)
 SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
-HEADERS = ["ce_plan.h", "ce_stage.h", "ce_segment.h", "ce_gold.h", "ce_estimate_kernel.h", "ce_narrow_kernel.h", "ce_inst.inc"]
-PUBLIC_HEADERS = ["ce_hip.h", "ce_denoise.h", "ce_dmrs.h", "ce_eq.h", "ce_demod.h", "ce_rm.h"]   # include/
-PUBLIC_HEADERS_TP = ["ce_tp.h"]   # include/: the transform de-precoder's, with SIGNATURES_TP below
-PUBLIC_HEADERS_LDPC = ["ce_ldpc.h"]   # include/: the LDPC decoder's, with SIGNATURES_LDPC below
-PUBLIC_HEADERS_TB = ["ce_tb.h"]   # include/: transport-block assembly's, with SIGNATURES_TB below
-PUBLIC_HEADERS_ENC = ["ce_enc.h"]   # include/: the transport-block encoder's, with SIGNATURES_ENC below
-PUBLIC_HEADERS_MOD = ["ce_mod.h"]   # include/: the modulator's, with SIGNATURES_MOD below
 
+
+def build_deps() -> list[Path]:
+    """What build() compares the libraries' age with: every source and header of csrc/, everything under include/, this file."""
+    return sorted(p for pat in ("*.hip", "*.h", "*.inc") for p in CSRC.glob(pat)) + sorted(p for p in INCLUDE.rglob("*") if p.is_file()) + [Path(__file__)]
+
+
+class Header(NamedTuple):
+    """One public header of include/: the ctypes mirror of every structure it defines, by its C name, and
+    entry point -> (restype, argtypes) for every function it declares."""
+    structs: dict
+    signatures: dict
+
+
+# The public headers in the order load() applies them; a stage registers here and in SOURCES, nowhere else
+# (tests/test_abi_conformance.py holds every entry against its header and the compiler's record layouts).
+REGISTRY: dict[str, Header] = {}
 CE_ABI_VERSION = 3
 CE_MAX_CDM, CE_MAX_HOPS, CE_MAX_SYMBOLS = 2, 2, 14
 SMOOTHING = {"none": 0, "mean": 1, "filter": 2, "mmse": 3}   # "mmse": extension, not in the reference
@@ -79,11 +89,10 @@ KERNEL_UNITS = ["ce_inst_narrow.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f
                 "ce_inst_reg_h2_f0.hip", "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip"]
 
 
-# One table per public header: entry point -> (restype, argtypes).  load() applies them; the EXPORTS_* lists are their keys.
 _int, _vp, _i64, _i32 = C.c_int, C.c_void_p, C.c_int64, C.c_int32
 _i64p, _fp, _P = C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER
 _BATCH = [_vp, _vp, _i64p, _vp, _i64p, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-SIGNATURES = {                                                                            # include/ce_hip.h
+REGISTRY["ce_hip.h"] = Header(structs={"ce_hop_desc": HopDesc, "ce_plan_desc": PlanDesc, "ce_plan_info": PlanInfo, "ce_plan_host_view": PlanHostView}, signatures={
     "ce_plan_create": (_int, [_P(PlanDesc), _P(_vp)]),
     "ce_plan_destroy": (None, [_vp]),
     "ce_plan_get_info": (_int, [_vp, _P(PlanInfo)]),
@@ -93,13 +102,12 @@ SIGNATURES = {                                                                  
     "ce_time_batch": (_int, _BATCH + [_i32, _i32, _P(C.c_double)]),
     "ce_last_error": (C.c_char_p, []),
     "ce_abi_version": (_int, []),
-}
-SIGNATURES_DENOISE = {                                                                    # include/ce_denoise.h (extension)
+})
+REGISTRY["ce_denoise.h"] = Header(structs={}, signatures={   # extension
     "ce_denoiser_create": (_int, [_i32, _fp, _fp, _fp, _fp, _fp, _fp, _P(_vp)]),
     "ce_denoiser_destroy": (None, [_vp]),
     "ce_denoise_batch": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
-}
-EXPORTS, EXPORTS_DENOISE = list(SIGNATURES), list(SIGNATURES_DENOISE)
+})
 CE_DMRS_MAX_WORDS, CE_DMRS_MAX_RE = 136, 2048
 
 
@@ -128,14 +136,13 @@ class DmrsHostView(C.Structure):
                 ("odd_sign", (C.c_uint8 * CE_DMRS_MAX_RE) * CE_MAX_HOPS)]
 
 
-SIGNATURES_DMRS = {                                                                       # include/ce_dmrs.h (extension)
+REGISTRY["ce_dmrs.h"] = Header(structs={"ce_dmrs_hop_desc": DmrsHopDesc, "ce_dmrs_desc": DmrsDesc, "ce_dmrs_info": DmrsInfo, "ce_dmrs_host_view": DmrsHostView}, signatures={   # extension
     "ce_dmrs_derive_host": (_int, [_P(DmrsDesc), _P(DmrsHostView)]),
     "ce_dmrs_plan_create": (_int, [_P(DmrsDesc), _P(_vp)]),
     "ce_dmrs_plan_destroy": (None, [_vp]),
     "ce_dmrs_plan_get_info": (_int, [_vp, _P(DmrsInfo)]),
     "ce_dmrs_generate": (_int, [_vp, _vp, _vp, _vp, _i64p, _i64, _vp, _vp]),
-}
-EXPORTS_DMRS = list(SIGNATURES_DMRS)
+})
 CE_EQ_MAX_PORTS, CE_EQ_CHUNK_SC = 8, 36
 
 
@@ -159,14 +166,13 @@ class EqHostView(C.Structure):
                 ("n_data_re", C.c_int32)]
 
 
-SIGNATURES_EQ = {                                                                         # include/ce_eq.h (extension)
+REGISTRY["ce_eq.h"] = Header(structs={"ce_eq_hop_desc": EqHopDesc, "ce_eq_desc": EqDesc, "ce_eq_info": EqInfo, "ce_eq_host_view": EqHostView}, signatures={   # extension
     "ce_eq_derive_host": (_int, [_P(EqDesc), _P(EqHostView)]),
     "ce_eq_plan_create": (_int, [_P(EqDesc), _P(_vp)]),
     "ce_eq_plan_destroy": (None, [_vp]),
     "ce_eq_plan_get_info": (_int, [_vp, _P(EqInfo)]),
     "ce_eq_equalize": (_int, [_vp, _vp, _i64p, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
-}
-EXPORTS_EQ = list(SIGNATURES_EQ)
+})
 CE_DEMOD_MAX_BITS, CE_DEMOD_BLOCK_WORDS, CE_DEMOD_TILE_SYMBOLS = 1 << 21, 8, 1024
 CE_DEMOD_OUT_F32, CE_DEMOD_OUT_I8 = 0, 1
 
@@ -185,15 +191,14 @@ class DemodHostView(C.Structure):
                 ("tile_symbols", C.c_int32), ("n_tiles", C.c_int32), ("table_bytes", C.c_int64)]
 
 
-SIGNATURES_DEMOD = {                                                                      # include/ce_demod.h (extension)
+REGISTRY["ce_demod.h"] = Header(structs={"ce_demod_desc": DemodDesc, "ce_demod_info": DemodInfo, "ce_demod_host_view": DemodHostView}, signatures={   # extension
     "ce_demod_derive_host": (_int, [_P(DemodDesc), _P(DemodHostView)]),
     "ce_demod_copy_tables": (_int, [_P(DemodDesc), _vp, _vp]),
     "ce_demod_plan_create": (_int, [_P(DemodDesc), _P(_vp)]),
     "ce_demod_plan_destroy": (None, [_vp]),
     "ce_demod_plan_get_info": (_int, [_vp, _P(DemodInfo)]),
     "ce_demod_demap": (_int, [_vp, _vp, _vp, _vp, _vp, _i64p, _i64, _vp, _vp]),
-}
-EXPORTS_DEMOD = list(SIGNATURES_DEMOD)
+})
 CE_RM_F32, CE_RM_I8, CE_RM_MAX_SLOT_ELEMS, CE_RM_TILE_UNITS = 0, 1, 1 << 24, 1024
 
 
@@ -216,14 +221,13 @@ class RmHostView(C.Structure):
                 ("tiles_per_block", C.c_int32), ("n_tiles", C.c_int32)]
 
 
-SIGNATURES_RM = {                                                                         # include/ce_rm.h (extension)
+REGISTRY["ce_rm.h"] = Header(structs={"ce_rm_desc": RmDesc, "ce_rm_info": RmInfo, "ce_rm_host_view": RmHostView}, signatures={   # extension
     "ce_rm_derive_host": (_int, [_P(RmDesc), _P(RmHostView)]),
     "ce_rm_plan_create": (_int, [_P(RmDesc), _P(_vp)]),
     "ce_rm_plan_destroy": (None, [_vp]),
     "ce_rm_plan_get_info": (_int, [_vp, _P(RmInfo)]),
     "ce_rm_recover": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
-}
-EXPORTS_RM = list(SIGNATURES_RM)
+})
 CE_TP_MAX_PRBS, CE_TP_MAX_PASSES = 275, 8
 
 
@@ -242,15 +246,14 @@ class TpHostView(C.Structure):
                 ("twiddle_bytes", C.c_int32), ("n_workgroups_per_slot", C.c_int32)]
 
 
-SIGNATURES_TP = {                                                                         # include/ce_tp.h (extension)
+REGISTRY["ce_tp.h"] = Header(structs={"ce_tp_desc": TpDesc, "ce_tp_info": TpInfo, "ce_tp_host_view": TpHostView}, signatures={   # extension
     "ce_tp_derive_host": (_int, [_P(TpDesc), _P(TpHostView)]),
     "ce_tp_copy_twiddles": (_int, [_P(TpDesc), _vp]),
     "ce_tp_plan_create": (_int, [_P(TpDesc), _P(_vp)]),
     "ce_tp_plan_destroy": (None, [_vp]),
     "ce_tp_plan_get_info": (_int, [_vp, _P(TpInfo)]),
     "ce_tp_deprecode": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-}
-EXPORTS_TP = list(SIGNATURES_TP)
+})
 CE_LDPC_MAX_ZC, CE_LDPC_MAX_ROWS, CE_LDPC_MAX_COLS, CE_LDPC_MAX_ROW_DEGREE = 384, 46, 68, 19
 CE_LDPC_L_BOUND, CE_LDPC_LDS_MAX, CE_LDPC_F32, CE_LDPC_I8 = 4497, 163840, 0, 1
 CE_LDPC_STATE_IDX_SHIFT, CE_LDPC_STATE_MAG_SHIFT = 19, 24
@@ -278,14 +281,13 @@ class LdpcHostView(C.Structure):
                 ("state_idx_shift", C.c_int32), ("state_mag_shift", C.c_int32)]
 
 
-SIGNATURES_LDPC = {                                                                       # include/ce_ldpc.h (extension)
+REGISTRY["ce_ldpc.h"] = Header(structs={"ce_ldpc_desc": LdpcDesc, "ce_ldpc_info": LdpcInfo, "ce_ldpc_host_view": LdpcHostView}, signatures={   # extension
     "ce_ldpc_derive_host": (_int, [_P(LdpcDesc), _P(LdpcHostView)]),
     "ce_ldpc_plan_create": (_int, [_P(LdpcDesc), _P(_vp)]),
     "ce_ldpc_plan_destroy": (None, [_vp]),
     "ce_ldpc_plan_get_info": (_int, [_vp, _P(LdpcInfo)]),
     "ce_ldpc_decode": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-}
-EXPORTS_LDPC = list(SIGNATURES_LDPC)
+})
 CE_TB_G24A, CE_TB_G24B, CE_TB_G16, CE_TB_THREADS, CE_TB_MAX_PIECE = 0x864CFB, 0x800063, 0x1021, 256, 5
 
 
@@ -306,14 +308,13 @@ class TbHostView(C.Structure):
                 ("power_bytes", C.c_int32)]
 
 
-SIGNATURES_TB = {                                                                         # include/ce_tb.h (extension)
+REGISTRY["ce_tb.h"] = Header(structs={"ce_tb_desc": TbDesc, "ce_tb_info": TbInfo, "ce_tb_host_view": TbHostView}, signatures={   # extension
     "ce_tb_derive_host": (_int, [_P(TbDesc), _P(TbHostView)]),
     "ce_tb_plan_create": (_int, [_P(TbDesc), _P(_vp)]),
     "ce_tb_plan_destroy": (None, [_vp]),
     "ce_tb_plan_get_info": (_int, [_vp, _P(TbInfo)]),
     "ce_tb_assemble": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-}
-EXPORTS_TB = list(SIGNATURES_TB)
+})
 CE_ENC_THREADS, CE_ENC_CORE_TRIANGULAR, CE_ENC_CORE_NR, CE_ENC_CRC_CHUNK = 256, 0, 1, 1024
 
 
@@ -340,16 +341,16 @@ class EncHostView(C.Structure):
                 ("table_bytes", C.c_int32)]
 
 
-SIGNATURES_ENC = {                                                                        # include/ce_enc.h (extension)
+REGISTRY["ce_enc.h"] = Header(structs={"ce_enc_desc": EncDesc, "ce_enc_info": EncInfo, "ce_enc_host_view": EncHostView}, signatures={   # extension
     "ce_enc_derive_host": (_int, [_P(EncDesc), _P(EncHostView)]),
     "ce_enc_plan_create": (_int, [_P(EncDesc), _P(_vp)]),
     "ce_enc_plan_destroy": (None, [_vp]),
     "ce_enc_plan_get_info": (_int, [_vp, _P(EncInfo)]),
     "ce_enc_encode": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
-}
-EXPORTS_ENC = list(SIGNATURES_ENC)
+})
 CE_MAX_LAYERS, CE_MOD_THREADS, CE_MOD_TILE_SC, CE_MOD_GROUP_SYMBOLS, CE_MOD_MAX_TILE_BLOCKS = 4, 256, 256, 7, 34
-CE_MOD_A = {2: 0x3F3504F3, 4: 0x3EA1E89B, 6: 0x3E1E01B3, 8: 0x3D9D130E}   # float32 bit patterns of A_qm
+CE_MOD_A_QPSK, CE_MOD_A_16QAM, CE_MOD_A_64QAM, CE_MOD_A_256QAM = 0x3F3504F3, 0x3EA1E89B, 0x3E1E01B3, 0x3D9D130E
+CE_MOD_A = {2: CE_MOD_A_QPSK, 4: CE_MOD_A_16QAM, 6: CE_MOD_A_64QAM, 8: CE_MOD_A_256QAM}   # float32 bit patterns of A_qm
 
 
 class ModHopDesc(C.Structure):
@@ -378,14 +379,15 @@ class ModHostView(C.Structure):
                 ("max_tile_blocks", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32)]
 
 
-SIGNATURES_MOD = {                                                                        # include/ce_mod.h (extension)
+REGISTRY["ce_mod.h"] = Header(structs={"ce_mod_hop_desc": ModHopDesc, "ce_mod_desc": ModDesc, "ce_mod_info": ModInfo, "ce_mod_host_view": ModHostView}, signatures={   # extension
     "ce_mod_derive_host": (_int, [_P(ModDesc), _P(ModHostView)]),
     "ce_mod_plan_create": (_int, [_P(ModDesc), _P(_vp)]),
     "ce_mod_plan_destroy": (None, [_vp]),
     "ce_mod_plan_get_info": (_int, [_vp, _P(ModInfo)]),
     "ce_mod_modulate": (_int, [_vp, _vp, _vp, _i64, C.c_float, _vp, _vp, _i64p, _i64, _vp, _vp]),
-}
-EXPORTS_MOD = list(SIGNATURES_MOD)
+})
+EXPORTS, EXPORTS_DENOISE = list(REGISTRY["ce_hip.h"].signatures), list(REGISTRY["ce_denoise.h"].signatures)
+ALL_EXPORTS = [name for header in REGISTRY.values() for name in header.signatures]
 
 
 # per-source compiler flags: the denoiser's MFMA results feed vector instructions straight away, so keep them in
@@ -414,7 +416,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: Path 
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / h for h in HEADERS] + [INCLUDE / h for h in PUBLIC_HEADERS + PUBLIC_HEADERS_TP + PUBLIC_HEADERS_LDPC + PUBLIC_HEADERS_TB + PUBLIC_HEADERS_ENC + PUBLIC_HEADERS_MOD] + [Path(__file__)]
+    deps = build_deps()
     shipped = CSRC / "libce_hip.so"                         # build() always writes the in-tree library, whatever CE_HIP_LIB selects for loading
     target = Path(out) if out is not None else shipped
     if out is None and not force and all(t.exists() and all(t.stat().st_mtime >= d.stat().st_mtime for d in deps) for t in (shipped, KNOBS_LIB_PATH)):
@@ -469,8 +471,8 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the estimator has no CPU fallback)")
     lib = C.CDLL(str(LIB_PATH))
-    for table in (SIGNATURES, SIGNATURES_DENOISE, SIGNATURES_DMRS, SIGNATURES_EQ, SIGNATURES_DEMOD, SIGNATURES_RM, SIGNATURES_TP, SIGNATURES_LDPC, SIGNATURES_TB, SIGNATURES_ENC, SIGNATURES_MOD):
-        for name, (restype, argtypes) in table.items():
+    for header in REGISTRY.values():
+        for name, (restype, argtypes) in header.signatures.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
     if lib.ce_abi_version() != CE_ABI_VERSION:

@@ -287,8 +287,7 @@ struct ce_demod_plan {
   bool i8 = false;
   ce_demod_info info{};
   DemodDev dev{};
-  uint32_t* x1 = nullptr;     // [n_blocks * DQ_BW]
-  uint32_t* jump = nullptr;   // [32][n_blocks]: rows 0 .. 30 = the entries of c_init bit i, row 31 = zeros
+  CeGoldDev gold;   // with descrambling: the tables of blocks of DQ_BW words
 };
 
 extern "C" int ce_demod_derive_host(const ce_demod_desc* d, ce_demod_host_view* v) {
@@ -329,13 +328,8 @@ extern "C" int ce_demod_plan_create(const ce_demod_desc* d, ce_demod_plan** out)
     *out = p.release();
     return CE_OK;
   }
-  std::vector<uint32_t> x1, j, rows((size_t)32 * v.n_blocks, 0u);
-  dq_tables(v, x1, j);
-  for (int blk = 0; blk < v.n_blocks; ++blk)
-    for (int i = 0; i < 31; ++i) rows[(size_t)i * v.n_blocks + blk] = j[(size_t)blk * 31 + i];
   CeDeviceScope scope(d->device);
-  hipError_t e = ce_upload(scope.err, &p->x1, x1.data(), x1.size() * sizeof(uint32_t));
-  e = ce_upload(e, &p->jump, rows.data(), rows.size() * sizeof(uint32_t));
+  const hipError_t e = ce_gold_upload(scope.err, (size_t)v.n_blocks, DQ_BW, &p->gold);
   if (e != hipSuccess) {
     ce_demod_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "demapper plan upload: %s", hipGetErrorString(e));
@@ -346,8 +340,7 @@ extern "C" int ce_demod_plan_create(const ce_demod_desc* d, ce_demod_plan** out)
 
 extern "C" void ce_demod_plan_destroy(ce_demod_plan* p) {
   if (!p) return;
-  if (p->x1) (void)hipFree(p->x1);
-  if (p->jump) (void)hipFree(p->jump);
+  ce_gold_free(&p->gold);
   delete p;
 }
 
@@ -372,10 +365,10 @@ extern "C" int ce_demod_demap(const ce_demod_plan* p, const void* x_hat, const f
   const int64_t s0 = descramble ? strides[0] : 0, s1 = descramble ? strides[1] : 0;
   const hipStream_t st = (hipStream_t)stream;
   switch (p->qm) {
-    case 2: dq_launch<2>(p->dev, p->i8, n_wg, p->x1, p->jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
-    case 4: dq_launch<4>(p->dev, p->i8, n_wg, p->x1, p->jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
-    case 6: dq_launch<6>(p->dev, p->i8, n_wg, p->x1, p->jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
-    default: dq_launch<8>(p->dev, p->i8, n_wg, p->x1, p->jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
+    case 2: dq_launch<2>(p->dev, p->i8, n_wg, p->gold.x1, p->gold.jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
+    case 4: dq_launch<4>(p->dev, p->i8, n_wg, p->gold.x1, p->gold.jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
+    case 6: dq_launch<6>(p->dev, p->i8, n_wg, p->gold.x1, p->gold.jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
+    default: dq_launch<8>(p->dev, p->i8, n_wg, p->gold.x1, p->gold.jump, x, nvar, rnti, n_id, s0, s1, out, st); break;
   }
   return ce_launch_status("demapper");
 }

@@ -6,7 +6,7 @@
 //  Bit strings.  Every bit string in LDS is a row of dwords holding bit b in bit 31 - (b mod 32) of dword b / 32, so a
 //   global row (MSB first in bytes) is the same dwords byte-swapped, and 32 bits from any bit position are two dwords and
 //   one funnel shift (enc_get32).
-//  CRC.  Registers hold a residue left-aligned in 32 bits, as in ce_tb.hip.  A string is cut into chunks of
+//  CRC.  Registers hold a residue left-aligned in 32 bits (ce_crc.h).  A string is cut into chunks of
 //   CE_ENC_CRC_CHUNK dwords; thread t runs dwords 4 t .. 4 t + 3 of every chunk through the CRC (one 16-byte load; four
 //   table lookups per dword from four 256-entry tables in LDS, the lookups of a dword independent of one another) and
 //   carries its residue from chunk to chunk by x^(32 (CHUNK - 4)).  The 256 residues are advanced by x^(128 (255 - t)),
@@ -37,7 +37,9 @@
 
 #include <vector>
 
+#include "ce_crc.h"
 #include "ce_enc.h"
+#include "ce_segment.h"
 #include "ce_stage.h"
 
 namespace {
@@ -69,34 +71,6 @@ struct EncDev {
   uint32_t two_zc;
 };
 
-// r(x) x mod g on left-aligned values
-__host__ __device__ __forceinline__ uint32_t enc_xtime(uint32_t r, uint32_t g) { return (r << 1) ^ ((uint32_t)((int32_t)r >> 31) & g); }
-
-// a(x) b(x) mod g for residues of L bits, left-aligned: Horner over the bits of b
-__host__ __device__ __forceinline__ uint32_t enc_mulmod(uint32_t a, uint32_t b, uint32_t g, uint32_t L) {
-  uint32_t r = 0;
-  for (uint32_t i = 0; i < L; ++i) {
-    r = enc_xtime(r, g) ^ ((uint32_t)((int32_t)b >> 31) & a);
-    b <<= 1;
-  }
-  return r;
-}
-
-// floor(a / d) and the remainder for a < 2^24, d >= 1, inv = float32(1 / d): ce_rm.hip's rm_divmod
-__device__ __forceinline__ void enc_divmod(uint32_t a, uint32_t d, float inv, uint32_t& quo, uint32_t& rem) {
-  uint32_t q = (uint32_t)((float)a * inv);
-  int32_t m = (int32_t)a - (int32_t)(q * d);
-  if (m < 0) {
-    --q;
-    m += (int32_t)d;
-  } else if (m >= (int32_t)d) {
-    ++q;
-    m -= (int32_t)d;
-  }
-  quo = q;
-  rem = (uint32_t)m;
-}
-
 // bits [pos, pos + 32) of a bit string; reads dwords pos / 32 and pos / 32 + 1
 __device__ __forceinline__ uint32_t enc_get32(const uint32_t* p, uint32_t pos) {
   const uint32_t d = pos >> 5, sh = pos & 31u;
@@ -118,12 +92,6 @@ __device__ __forceinline__ uint32_t enc_periodic32(const uint32_t* p, uint32_t o
   return (uint32_t)((x << m) >> 32);
 }
 
-__device__ __forceinline__ uint32_t enc_wave_xor(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v ^= (uint32_t)__shfl_xor((int)v, off);
-  return v;
-}
-
 __device__ __forceinline__ uint32_t enc_crc_dword(uint32_t v, const uint32_t (*T)[256]) {
   // v(x) x^L mod g: the one data-dependent address, masked to the table's size
   return T[3][v >> 24] ^ T[2][(v >> 16) & 255u] ^ T[1][(v >> 8) & 255u] ^ T[0][v & 255u];
@@ -138,16 +106,16 @@ __device__ __forceinline__ uint32_t enc_crc(const uint32_t (*T)[256], uint32_t g
 #pragma unroll 4
   for (uint32_t c = 0; c < n_chunks; ++c) {
     const uint4 d = fetch(c * (uint32_t)ENC_NT + threadIdx.x);
-    if (c) acc = enc_mulmod(acc, xc, g, L);
+    if (c) acc = ce_crc_mulmod(acc, xc, g, L);
     acc = enc_crc_dword(acc ^ d.x, T);
     acc = enc_crc_dword(acc ^ d.y, T);
     acc = enc_crc_dword(acc ^ d.z, T);
     acc = enc_crc_dword(acc ^ d.w, T);
   }
-  acc = enc_wave_xor(enc_mulmod(acc, pw, g, L));
+  acc = ce_crc_wave_xor(ce_crc_mulmod(acc, pw, g, L));
   if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  return enc_mulmod(red[0] ^ red[1] ^ red[2] ^ red[3], finv, g, L);
+  return ce_crc_mulmod(red[0] ^ red[1] ^ red[2] ^ red[3], finv, g, L);
 }
 
 // the rank the walk of redundancy version rv & 3 starts at
@@ -176,7 +144,7 @@ __device__ __forceinline__ uint32_t enc_gather_dword(const EncDev& P, uint32_t d
   uint32_t val = 0u;
   for (uint32_t b = 0; b < nb; ++b) {
     uint32_t k = i * eq + j, q;
-    if (P.rep) enc_divmod(k, P.prm, P.inv_prm, q, k);   // repetition wraps round the buffer
+    if (P.rep) ce_divmod(k, P.prm, P.inv_prm, q, k);   // repetition wraps round the buffer
     uint32_t rho = s + k;
     if (rho >= P.prm) rho -= P.prm;
     const uint32_t pos = (rho < P.f0 ? rho : rho + P.nf) + P.two_zc;
@@ -215,7 +183,7 @@ __global__ __launch_bounds__(ENC_NT) void ce_enc_kernel(EncDev P, const uint32_t
     uint32_t v = t << 24;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      for (int q = 0; q < 8; ++q) v = enc_xtime(v, gp);
+      for (int q = 0; q < 8; ++q) v = ce_crc_xtime(v, gp);
       s_crc[which][k][t] = v;
     }
   }
@@ -398,13 +366,9 @@ int enc_derive(const ce_enc_desc* d, ce_enc_host_view* v, EncGraph* out) {
   v->zc = rm.zc, v->k = rm.k, v->n = rm.n, v->n_cb = rm.n_cb, v->f0 = rm.f0, v->f1 = rm.f1, v->p_rm = rm.p;
   v->n_lo = rm.n_lo, v->e_lo = rm.e_lo, v->e_hi = rm.e_hi;
   for (int i = 0; i < 4; ++i) v->k0[i] = rm.k0[i], v->s[i] = rm.s[i];
-  const bool crc24 = d->tbs > 3824;
-  v->l_tb = crc24 ? 24 : 16;
-  v->l_cb = rm.c > 1 ? 24 : 0;
-  v->p = rm.k_prime - v->l_cb;
-  v->g_tb = crc24 ? CE_TB_G24A : CE_TB_G16;
-  v->g_cb = CE_TB_G24B;
-  v->tb_row_bytes = 16 * (int32_t)(((int64_t)d->tbs + 127) / 128);
+  const CeCrcSelect crc = ce_crc_select(d->tbs, rm.c, rm.k_prime);
+  v->l_tb = crc.l_tb, v->l_cb = crc.l_cb, v->p = crc.p, v->g_tb = crc.g_tb, v->g_cb = crc.g_cb;
+  v->tb_row_bytes = crc.tb_row_bytes;
   v->g_row_bytes = 16 * ((d->g_bits + 127) / 128);
 
   // ---- the graph ----
@@ -520,18 +484,11 @@ int enc_derive(const ce_enc_desc* d, ce_enc_host_view* v, EncGraph* out) {
   return CE_OK;
 }
 
-// x^e mod g, left-aligned
-uint32_t enc_pow_x(uint32_t one, uint32_t g, int64_t e) {
-  uint32_t r = one;
-  for (int64_t i = 0; i < e; ++i) r = enc_xtime(r, g);
-  return r;
-}
-
 // x^-e mod g: x h(x) = 1 for h = (g + 1) / x, g taken with its leading term
 uint32_t enc_pow_x_inv(uint32_t g, uint32_t L, int64_t e) {
   const uint32_t one = 1u << (32u - L), h = 0x80000000u | (((g >> (32u - L)) >> 1) << (32u - L));   // left-aligned: x^(L-1) + (g_low >> 1)
   uint32_t r = one;
-  for (int64_t i = 0; i < e; ++i) r = enc_mulmod(r, h, g, L);
+  for (int64_t i = 0; i < e; ++i) r = ce_crc_mulmod(r, h, g, L);
   return r;
 }
 
@@ -574,11 +531,11 @@ extern "C" int ce_enc_plan_create(const ce_enc_desc* d, ce_enc_plan** out) {
   const uint32_t one_tb = 1u << (32u - D.l_tb), one_cb = 1u << 8;
   const int64_t chunk_bits = 32 * (int64_t)ENC_CHUNK;
   D.nc_tb = (uint32_t)((d->tbs + chunk_bits - 1) / chunk_bits);
-  D.xc_tb = enc_pow_x(one_tb, D.g_tb, 32 * (int64_t)(ENC_CHUNK - 4));
+  D.xc_tb = ce_crc_pow_x(one_tb, D.g_tb, 32 * (int64_t)(ENC_CHUNK - 4));
   D.finv_tb = enc_pow_x_inv(D.g_tb, D.l_tb, D.nc_tb * chunk_bits - d->tbs);
   D.finv_cb = enc_pow_x_inv(D.g_cb, 24u, chunk_bits - v.p);
-  if (enc_mulmod(enc_pow_x(one_tb, D.g_tb, 1), enc_pow_x_inv(D.g_tb, D.l_tb, 1), D.g_tb, D.l_tb) != one_tb ||
-      enc_mulmod(enc_pow_x(one_cb, D.g_cb, 1), enc_pow_x_inv(D.g_cb, 24u, 1), D.g_cb, 24u) != one_cb)
+  if (ce_crc_mulmod(ce_crc_pow_x(one_tb, D.g_tb, 1), enc_pow_x_inv(D.g_tb, D.l_tb, 1), D.g_tb, D.l_tb) != one_tb ||
+      ce_crc_mulmod(ce_crc_pow_x(one_cb, D.g_cb, 1), enc_pow_x_inv(D.g_cb, 24u, 1), D.g_cb, 24u) != one_cb)
     return ce_fail(CE_ERR_INVALID, "internal: x has no inverse modulo the CRC polynomial");
   D.tb_row_dwords = (uint32_t)v.tb_row_bytes / 4u, D.g_row_dwords = (uint32_t)v.g_row_bytes / 4u, D.cw_row_dwords = (uint32_t)v.cw_row_bytes / 4u;
   D.zc = (uint32_t)v.zc, D.n_sys = (uint32_t)v.n_sys, D.n_rows = (uint32_t)d->n_rows, D.w = (uint32_t)v.col_dwords, D.we = (uint32_t)v.ext_dwords;
@@ -596,11 +553,11 @@ extern "C" int ce_enc_plan_create(const ce_enc_desc* d, ce_enc_plan** out) {
   T.resize(D.graph_dw + 512);
   const uint32_t gs[2] = {D.g_tb, D.g_cb}, Ls[2] = {D.l_tb, 24u}, ones[2] = {one_tb, one_cb};
   for (int w = 0; w < 2; ++w) {
-    const uint32_t x128 = enc_pow_x(ones[w], gs[w], 128);
+    const uint32_t x128 = ce_crc_pow_x(ones[w], gs[w], 128);
     uint32_t cur = ones[w];
     for (int t = 255; t >= 0; --t) {
       T[D.graph_dw + 256 * w + t] = cur;
-      cur = enc_mulmod(cur, x128, gs[w], Ls[w]);
+      cur = ce_crc_mulmod(cur, x128, gs[w], Ls[w]);
     }
   }
   CeDeviceScope scope(d->device);

@@ -309,12 +309,6 @@ void eq_launch(const ce_eq_plan* p, unsigned n_wg, size_t lds, const float2* rx,
 
 // ---- host derivation: integers only ----
 
-int eq_popcount12(unsigned m) {
-  int n = 0;
-  for (int r = 0; r < 12; ++r) n += (m >> r) & 1u;
-  return n;
-}
-
 int eq_derive(const ce_eq_desc* d, ce_eq_host_view* v) {
   memset(v, 0, sizeof(*v));
   for (int s = 0; s < CE_MAX_SYMBOLS; ++s) v->sym_hop[s] = -1;
@@ -334,7 +328,7 @@ int eq_derive(const ce_eq_desc* d, ce_eq_host_view* v) {
       if (v->sym_hop[s] >= 0) return ce_fail(CE_ERR_UNSUPPORTED, "hops %d and %d share OFDM symbol %d", v->sym_hop[s], h, s);
       v->sym_hop[s] = h;
       v->data_mask[s] = hd.dmrs_symbols[s] ? (int32_t)(0xFFFu & ~(unsigned)hd.reserved_re_mask) : 0xFFF;
-      v->data_res_per_prb[s] = eq_popcount12((unsigned)v->data_mask[s]);
+      v->data_res_per_prb[s] = ce_popcount12((unsigned)v->data_mask[s]);
     }
   }
   // output order: symbol ascending, subcarrier ascending.  Every data RE is walked through the kernel's row formula.
@@ -346,7 +340,7 @@ int eq_derive(const ce_eq_desc* d, ce_eq_host_view* v) {
     for (int q = hd.prb_start; q < hd.prb_start + hd.n_prbs; ++q)
       for (int re = 0; re < 12; ++re)
         if ((v->data_mask[s] >> re) & 1) {
-          const int64_t row = v->first_row[s] + (int64_t)(q - hd.prb_start) * v->data_res_per_prb[s] + eq_popcount12((unsigned)v->data_mask[s] & ((1u << re) - 1u));
+          const int64_t row = v->first_row[s] + (int64_t)(q - hd.prb_start) * v->data_res_per_prb[s] + ce_popcount12((unsigned)v->data_mask[s] & ((1u << re) - 1u));
           if (row != n) return ce_fail(CE_ERR_UNSUPPORTED, "row formula gives %lld for data RE %lld", (long long)row, (long long)n);
           ++n;
         }

@@ -5,6 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "ce_stage.h"
+
 constexpr int CE_GOLD_NC_WORDS = 50;   // Nc = 1600 bits = 50 words
 
 // One word (32 steps) of a length-31 LFSR whose feedback is x(n + 31) = XOR of x(n + t) over the taps: x1 has taps {0, 3},
@@ -52,4 +56,26 @@ inline void ce_gold_block_tables(size_t n_blocks, int block_words, Vec& x1, Vec&
       for (int k = 0; k < block_words; ++k) (void)ce_gold_step_word<true>(s);
     }
   }
+}
+
+// Those tables on the device, as the kernels read them.
+struct CeGoldDev {
+  uint32_t* x1 = nullptr;     // [n_blocks * block_words]
+  uint32_t* jump = nullptr;   // [32][n_blocks]: rows 0 .. 30 = the entries of c_init bit i, row 31 = zeros
+};
+
+// Host: the next two links of a plan's upload chain (ce_stage.h) -- builds the tables, turns jump block-fastest and uploads
+// the pair to the current device.  The pointers stay the plan's to free (ce_gold_free) either way.
+inline hipError_t ce_gold_upload(hipError_t e, size_t n_blocks, int block_words, CeGoldDev* t) {
+  std::vector<uint32_t> x1, j, rows(32 * n_blocks, 0u);
+  ce_gold_block_tables(n_blocks, block_words, x1, j);
+  for (size_t blk = 0; blk < n_blocks; ++blk)
+    for (int i = 0; i < 31; ++i) rows[(size_t)i * n_blocks + blk] = j[blk * 31 + i];
+  e = ce_upload(e, &t->x1, x1.data(), x1.size() * sizeof(uint32_t));
+  return ce_upload(e, &t->jump, rows.data(), rows.size() * sizeof(uint32_t));
+}
+
+inline void ce_gold_free(CeGoldDev* t) {
+  if (t->x1) (void)hipFree(t->x1);
+  if (t->jump) (void)hipFree(t->jump);
 }

@@ -205,13 +205,7 @@ __global__ __launch_bounds__(MOD_NT) void ce_mod_kernel(ModDev P, const uint4* _
 
 // ---- host derivation: integers only ----
 
-int mod_popcount12(unsigned m) {
-  int n = 0;
-  for (int r = 0; r < 12; ++r) n += (m >> r) & 1u;
-  return n;
-}
-
-int mod_rows_before_host(int d, int dmask, int dpp) { return (d / 12) * dpp + mod_popcount12((unsigned)dmask & ((1u << (d % 12)) - 1u)); }
+int mod_rows_before_host(int d, int dmask, int dpp) { return (d / 12) * dpp + ce_popcount12((unsigned)dmask & ((1u << (d % 12)) - 1u)); }
 
 int mod_derive(const ce_mod_desc* d, ce_mod_host_view* v) {
   memset(v, 0, sizeof(*v));
@@ -232,7 +226,7 @@ int mod_derive(const ce_mod_desc* d, ce_mod_host_view* v) {
   }
   ce_eq_host_view ev;
   if (const int rc = ce_eq_derive_host(&eq, &ev); rc != CE_OK) return rc;   // its text stands
-  const int n_cdm = (d->n_layers + 1) / 2, ppp = mod_popcount12(d->hop[0].re_mask[0]);
+  const int n_cdm = (d->n_layers + 1) / 2, ppp = ce_popcount12(d->hop[0].re_mask[0]);
   int col = 0;
   for (int h = 0; h < d->n_hops; ++h) {
     const ce_mod_hop_desc& hd = d->hop[h];
@@ -256,7 +250,7 @@ int mod_derive(const ce_mod_desc* d, ce_mod_host_view* v) {
       if (m == 0 || m > 0xFFFu) return ce_fail(CE_ERR_INVALID, "hop %d: re_mask[%d]=0x%x is not a non-empty 12-bit RE mask", h, c, m);
       if (m & ~(unsigned)hd.reserved_re_mask)
         return ce_fail(CE_ERR_INVALID, "hop %d: re_mask[%d]=0x%x lies outside reserved_re_mask=0x%x: an RE would carry a pilot and data", h, c, m, hd.reserved_re_mask);
-      if (mod_popcount12(m) != ppp) return ce_fail(CE_ERR_INVALID, "hop %d: re_mask[%d]=0x%x has %d REs, hop 0's re_mask[0] has %d", h, c, m, mod_popcount12(m), ppp);
+      if (ce_popcount12(m) != ppp) return ce_fail(CE_ERR_INVALID, "hop %d: re_mask[%d]=0x%x has %d REs, hop 0's re_mask[0] has %d", h, c, m, ce_popcount12(m), ppp);
     }
   }
   const int64_t G = (int64_t)ev.n_data_re * d->n_layers * d->qm;
@@ -319,8 +313,7 @@ struct ce_mod_plan {
   ce_mod_info info{};
   ModDev dev{};
   uint4* symtab = nullptr;    // [CE_MAX_SYMBOLS]
-  uint32_t* x1 = nullptr;     // [n_blocks * MOD_BW]
-  uint32_t* jump = nullptr;   // [32][n_blocks]: rows 0 .. 30 = the entries of c_init bit i, row 31 = zeros
+  CeGoldDev gold;             // with scrambling: the tables of blocks of MOD_BW words
 };
 
 extern "C" int ce_mod_derive_host(const ce_mod_desc* d, ce_mod_host_view* v) {
@@ -355,14 +348,7 @@ extern "C" int ce_mod_plan_create(const ce_mod_desc* d, ce_mod_plan** out) {
   }
   CeDeviceScope scope(d->device);
   hipError_t e = ce_upload(scope.err, &p->symtab, tab, sizeof(tab));
-  if (d->scramble) {
-    std::vector<uint32_t> x1, j, rows((size_t)32 * v.n_blocks, 0u);
-    ce_gold_block_tables((size_t)v.n_blocks, MOD_BW, x1, j);
-    for (int blk = 0; blk < v.n_blocks; ++blk)
-      for (int i = 0; i < 31; ++i) rows[(size_t)i * v.n_blocks + blk] = j[(size_t)blk * 31 + i];
-    e = ce_upload(e, &p->x1, x1.data(), x1.size() * sizeof(uint32_t));
-    e = ce_upload(e, &p->jump, rows.data(), rows.size() * sizeof(uint32_t));
-  }
+  if (d->scramble) e = ce_gold_upload(e, (size_t)v.n_blocks, MOD_BW, &p->gold);
   if (e != hipSuccess) {
     ce_mod_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "modulator plan upload: %s", hipGetErrorString(e));
@@ -374,8 +360,7 @@ extern "C" int ce_mod_plan_create(const ce_mod_desc* d, ce_mod_plan** out) {
 extern "C" void ce_mod_plan_destroy(ce_mod_plan* p) {
   if (!p) return;
   if (p->symtab) (void)hipFree(p->symtab);
-  if (p->x1) (void)hipFree(p->x1);
-  if (p->jump) (void)hipFree(p->jump);
+  ce_gold_free(&p->gold);
   delete p;
 }
 
@@ -404,10 +389,10 @@ extern "C" int ce_mod_modulate(const ce_mod_plan* p, const uint8_t* g, const voi
   float2* out = reinterpret_cast<float2*>(tx);
   const hipStream_t st = (hipStream_t)stream;
   switch (p->qm) {
-    case 2: mod_launch<2>(P, n_wg, p->symtab, p->x1, p->jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
-    case 4: mod_launch<4>(P, n_wg, p->symtab, p->x1, p->jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
-    case 6: mod_launch<6>(P, n_wg, p->symtab, p->x1, p->jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
-    default: mod_launch<8>(P, n_wg, p->symtab, p->x1, p->jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
+    case 2: mod_launch<2>(P, n_wg, p->symtab, p->gold.x1, p->gold.jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
+    case 4: mod_launch<4>(P, n_wg, p->symtab, p->gold.x1, p->gold.jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
+    case 6: mod_launch<6>(P, n_wg, p->symtab, p->gold.x1, p->gold.jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
+    default: mod_launch<8>(P, n_wg, p->symtab, p->gold.x1, p->gold.jump, g, pil, pilot_slot_stride, beta_dmrs, rnti, n_id, s0, s1, out, st); break;
   }
   return ce_launch_status("modulator");
 }

@@ -55,22 +55,6 @@ struct RmDev {
   float filler;                   // float32 format: the filler value
 };
 
-// floor(a / d) and a - d floor(a / d) for a < 2^24 and d >= 1, inv = float32(1 / d): the product is within one of the
-// quotient, one correction step either way makes it exact.
-__host__ __device__ __forceinline__ void rm_divmod(uint32_t a, uint32_t d, float inv, uint32_t& quo, uint32_t& rem) {
-  uint32_t q = (uint32_t)((float)a * inv);
-  int32_t m = (int32_t)a - (int32_t)(q * d);
-  if (m < 0) {
-    --q;
-    m += (int32_t)d;
-  } else if (m >= (int32_t)d) {
-    ++q;
-    m -= (int32_t)d;
-  }
-  quo = q;
-  rem = (uint32_t)m;
-}
-
 template <bool I8>
 __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __restrict__ llr_, const int32_t* __restrict__ rv, int64_t rv_stride,
                                                       uint32_t n_slots, const void* harq_, void* out_) {
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
     uint32_t k = rank >= s ? rank - s : rank + P.p - s;
     if (k >= P.p) k -= P.p;   // rank = P where the fillers run to the buffer's end (N_cb = K - 2 Zc): no position follows
     uint32_t j, i;
-    rm_divmod(k, eq, inv, j, i);
+    ce_divmod(k, eq, inv, j, i);
     k_first[h] = k;
     hits[h] = 0u;
 #pragma unroll
@@ -172,7 +156,7 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
           if (e_r > P.p) {   // repetition: k + P, k + 2 P, ..
             for (uint32_t k2 = k + P.p; k2 < e_r; k2 += P.p) {
               uint32_t j2, i2;
-              rm_divmod(k2, eq, inv, j2, i2);
+              ce_divmod(k2, eq, inv, j2, i2);
               acc += (Acc)row[i2 * P.qm + j2];
             }
           }

@@ -6,6 +6,13 @@
 
 #include "ce_plan.h"
 
+// REs set in the 12-bit mask of a PRB (the equalizer's and the modulator's derivations).
+inline int ce_popcount12(unsigned m) {
+  int n = 0;
+  for (int r = 0; r < 12; ++r) n += (m >> r) & 1u;
+  return n;
+}
+
 // A default-constructed plan, or null (the caller reports CE_ERR_NOMEM).
 template <class Plan>
 std::unique_ptr<Plan> ce_new_plan() {

@@ -35,6 +35,7 @@
 
 #include <vector>
 
+#include "ce_crc.h"
 #include "ce_segment.h"
 #include "ce_stage.h"
 #include "ce_tb.h"
@@ -57,19 +58,6 @@ struct TbDev {
   uint32_t piece, in_row_dwords;    // dwords per lane, dwords per row
   uint32_t tb_row_dwords;
 };
-
-// r(x) x mod g on left-aligned values
-__host__ __device__ __forceinline__ uint32_t tb_xtime(uint32_t r, uint32_t g) { return (r << 1) ^ ((uint32_t)((int32_t)r >> 31) & g); }
-
-// a(x) b(x) mod g for residues of L bits, left-aligned: Horner over the bits of b
-__host__ __device__ __forceinline__ uint32_t tb_mulmod(uint32_t a, uint32_t b, uint32_t g, uint32_t L) {
-  uint32_t r = 0;
-  for (uint32_t i = 0; i < L; ++i) {
-    r = tb_xtime(r, g) ^ ((uint32_t)((int32_t)b >> 31) & a);
-    b <<= 1;
-  }
-  return r;
-}
 
 __device__ __forceinline__ uint32_t tb_step_byte(uint32_t reg, uint32_t byte, const uint32_t* tab, uint32_t lane) {
 #ifdef CE_TB_NIBBLE
@@ -101,12 +89,6 @@ __device__ __forceinline__ void tb_keep_leading(const uint32_t (&w)[TB_MAXP], in
   }
 }
 
-__device__ __forceinline__ uint32_t tb_wave_xor(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v ^= (uint32_t)__shfl_xor((int)v, off);
-  return v;
-}
-
 // The lane's part of the block's residues: its piece w (big-endian dwords) cut at P for the transport-block polynomial
 // (times the power that also carries the block's x^((C-1-r) P)) and, with MULTI, at K' for CRC24B.
 template <bool MULTI, int PIECE>
@@ -127,10 +109,10 @@ __device__ __forceinline__ void tb_residues(const TbDev& P, const uint32_t* __re
   const uint32_t L = MULTI ? 24u : P.l_tb;
   uint32_t r_tb = 0u, r_cb = 0u;
   for (uint32_t i = 0; i < L; ++i) {
-    r_tb = tb_xtime(r_tb, P.g_tb) ^ ((uint32_t)((int32_t)b_tb >> 31) & a_tb);
+    r_tb = ce_crc_xtime(r_tb, P.g_tb) ^ ((uint32_t)((int32_t)b_tb >> 31) & a_tb);
     b_tb <<= 1;
     if constexpr (MULTI) {
-      r_cb = tb_xtime(r_cb, P.g_cb) ^ ((uint32_t)((int32_t)b_cb >> 31) & a_cb);
+      r_cb = ce_crc_xtime(r_cb, P.g_cb) ^ ((uint32_t)((int32_t)b_cb >> 31) & a_cb);
       b_cb <<= 1;
     }
   }
@@ -157,10 +139,10 @@ __global__ __launch_bounds__(TB_NT) void ce_tb_kernel(TbDev P, const uint32_t* _
     const uint32_t which = i / TB_TAB, e = i % TB_TAB, g = which ? P.g_cb : P.g_tb;
 #ifdef CE_TB_NIBBLE
     uint32_t v = (e >> 5) << 28;
-    for (int k = 0; k < 4; ++k) v = tb_xtime(v, g);
+    for (int k = 0; k < 4; ++k) v = ce_crc_xtime(v, g);
 #else
     uint32_t v = e << 24;
-    for (int k = 0; k < 8; ++k) v = tb_xtime(v, g);
+    for (int k = 0; k < 8; ++k) v = ce_crc_xtime(v, g);
 #endif
     tab[which][e] = v;
   }
@@ -204,8 +186,8 @@ __global__ __launch_bounds__(TB_NT) void ce_tb_kernel(TbDev P, const uint32_t* _
     TB_CASE(1) TB_CASE(2) TB_CASE(3) TB_CASE(4) TB_CASE(5)
   }
 #undef TB_CASE
-  const uint32_t t_r = tb_wave_xor(part_tb) >> P.sh_tb;
-  const uint32_t res = multi ? tb_wave_xor(part_cb) >> 8 : t_r;
+  const uint32_t t_r = ce_crc_wave_xor(part_tb) >> P.sh_tb;
+  const uint32_t res = multi ? ce_crc_wave_xor(part_cb) >> 8 : t_r;
   if (lane == 0) {
     reinterpret_cast<int2*>(cb_status)[blk] = make_int2((int)res, (int)t_r);
     if (!multi) reinterpret_cast<int2*>(tb_status)[slot] = make_int2((int)res, res != 0u ? 1 : 0);
@@ -224,7 +206,7 @@ __global__ __launch_bounds__(TB_NT) void ce_tb_fold_kernel(uint32_t c, uint32_t 
     x ^= (uint32_t)v.y;
     bad += v.x != 0 ? 1u : 0u;
   }
-  x = tb_wave_xor(x);
+  x = ce_crc_wave_xor(x);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) bad += (uint32_t)__shfl_xor((int)bad, off);
   if (lane == 0) reinterpret_cast<int2*>(tb_status)[slot] = make_int2((int)x, (int)bad);
@@ -239,19 +221,15 @@ int tb_derive(const ce_tb_desc* d, ce_tb_host_view* v) {
   if (d->tbs < 1) return ce_fail(CE_ERR_INVALID, "tbs=%d must be positive", d->tbs);
   CeSegment seg;
   if (const int rc = ce_segment_derive(d->base_graph, d->tbs, &seg); rc != CE_OK) return rc;
-  const bool crc24 = d->tbs > 3824;
+  const CeCrcSelect crc = ce_crc_select(d->tbs, seg.c, seg.k_prime);
   v->b = (int32_t)seg.b;
   v->k_cb = (int32_t)seg.k_cb;
   v->c = (int32_t)seg.c;
   v->b_prime = (int32_t)seg.b_prime;
   v->k_prime = (int32_t)seg.k_prime;
-  v->l_tb = crc24 ? 24 : 16;
-  v->l_cb = seg.c > 1 ? 24 : 0;
-  v->p = v->k_prime - v->l_cb;
-  v->g_tb = crc24 ? CE_TB_G24A : CE_TB_G16;
-  v->g_cb = CE_TB_G24B;
+  v->l_tb = crc.l_tb, v->l_cb = crc.l_cb, v->p = crc.p, v->g_tb = crc.g_tb, v->g_cb = crc.g_cb;
   v->in_row_bytes = 16 * ((v->k_prime + 127) / 128);
-  v->tb_row_bytes = 16 * (int32_t)(((int64_t)d->tbs + 127) / 128);
+  v->tb_row_bytes = crc.tb_row_bytes;
   v->piece_dwords = (v->in_row_bytes + 255) / 256;   // K' <= K_b 384 <= 8448: at most CE_TB_MAX_PIECE
   v->threads = TB_NT;
   v->blocks_per_workgroup = TB_BPW;
@@ -261,22 +239,15 @@ int tb_derive(const ce_tb_desc* d, ce_tb_host_view* v) {
   return CE_OK;
 }
 
-// x^e mod g, left-aligned
-uint32_t tb_pow_x(uint32_t one, uint32_t g, int64_t e) {
-  uint32_t r = one;
-  for (int64_t i = 0; i < e; ++i) r = tb_xtime(r, g);
-  return r;
-}
-
 // dst[l], l < 64: base x^(bits of the first n that follow piece l of W bits) -- x^(n mod W + W (f - 1 - l)) for the
 // f = floor(n / W) whole pieces, 1 for the partial piece (and whatever lies behind it, whose residue is 0)
 void tb_lane_powers(uint32_t* dst, uint32_t base, uint32_t one, uint32_t g, uint32_t L, uint32_t n, uint32_t W) {
-  const uint32_t f = n / W, xw = tb_pow_x(one, g, W);
+  const uint32_t f = n / W, xw = ce_crc_pow_x(one, g, W);
   for (uint32_t l = f; l < 64; ++l) dst[l] = base;
-  uint32_t t = tb_mulmod(base, tb_pow_x(one, g, n % W), g, L);
+  uint32_t t = ce_crc_mulmod(base, ce_crc_pow_x(one, g, n % W), g, L);
   for (uint32_t l = f; l-- > 0;) {
     dst[l] = t;
-    t = tb_mulmod(t, xw, g, L);
+    t = ce_crc_mulmod(t, xw, g, L);
   }
 }
 
@@ -322,11 +293,11 @@ extern "C" int ce_tb_plan_create(const ce_tb_desc* d, ce_tb_plan** out) {
   const uint32_t one_tb = 1u << D.sh_tb, one_cb = 1u << 8, W = 32u * D.piece;
   std::vector<uint32_t> pw((size_t)v.power_bytes / 4);
   tb_lane_powers(pw.data(), one_cb, one_cb, D.g_cb, 24u, D.kp, W);
-  const uint32_t xp = tb_pow_x(one_tb, D.g_tb, D.p);
+  const uint32_t xp = ce_crc_pow_x(one_tb, D.g_tb, D.p);
   uint32_t base = one_tb;   // x^((C-1-r) P)
   for (int64_t r = (int64_t)D.c - 1; r >= 0; --r) {
     tb_lane_powers(pw.data() + 64 * (r + 1), base, one_tb, D.g_tb, D.l_tb, D.p, W);
-    base = tb_mulmod(base, xp, D.g_tb, D.l_tb);
+    base = ce_crc_mulmod(base, xp, D.g_tb, D.l_tb);
   }
   CeDeviceScope scope(d->device);
   const hipError_t e = ce_upload(scope.err, &p->pw, pw.data(), pw.size() * sizeof(uint32_t));

@@ -3,8 +3,6 @@ anchors the operator was specified with, the library's host derivation (jump tab
 as the kernel combines them) against that oracle bit for bit, descriptor / parameter errors, and the OCC / CDM
 conventions against the estimator's CPU oracle.  No GPU."""
 import ctypes as C
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import dmrs_oracle as D
 from dmrs_oracle import CASE_A, CASE_B, CASE_C, T1, T2
 from srsran_ce_pytorch_amd import _lib, dmrs, synth as S
 
-ROOT = Path(__file__).resolve().parents[1]
 ANCHOR_HASH = {"A": ((18, 2, 1), "d82ca518f1c74f67"), "B": ((18, 4, 4), "bb224eab249c29f3"), "C": ((28, 1, 3), "3ffe9a508323217a")}
 CASES = [   # (case, slot, n_id, n_scid, n_symb_slot, grid_start_crb)
     CASE_A, CASE_B, CASE_C,
@@ -35,18 +32,12 @@ def lib():
 
 
 def test_library_exports_every_declared_dmrs_symbol(lib):
-    header = (ROOT / "include" / "ce_dmrs.h").read_text()
-    declared = set(re.findall(r"^\s*(?:const\s+char\s*\*|int|void)\s+(ce_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.EXPORTS_DMRS), declared ^ set(_lib.EXPORTS_DMRS)
-    for sym in declared:
-        assert hasattr(lib, sym), sym
-    assert not declared & set(_lib.EXPORTS) and lib.ce_abi_version() == 3
+    """The header against the binding: tests/test_abi_conformance.py.  Here: the sizes this stage's header implies."""
+    assert "ce_dmrs.h" in _lib.REGISTRY and "ce_dmrs.hip" in _lib.SOURCES
     # LP64 sizes implied by the header: hop 14 + 2*2 (+6 pad) + 8 = 32; desc 8*4 + 2*32 = 96; info 4 + 4 + 8 = 16
     assert (C.sizeof(_lib.DmrsHopDesc), C.sizeof(_lib.DmrsDesc), C.sizeof(_lib.DmrsInfo)) == (32, 96, 16)
     # view: 4*4 + 2*14*4 + 2*2*4 + 2*136*4 (x1) + 2*31*136*4 (t) + 2*2048*4 (m) + 2*2048 (odd_sign)
     assert C.sizeof(_lib.DmrsHostView) == 16 + 112 + 16 + 1088 + 33728 + 16384 + 4096
-    for name, val in (("CE_DMRS_MAX_WORDS", _lib.CE_DMRS_MAX_WORDS), ("CE_DMRS_MAX_RE", _lib.CE_DMRS_MAX_RE)):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == val
 
 
 def test_oracle_reproduces_the_gold_anchors():

@@ -40,28 +40,11 @@ def _view(name, graph=None):
 
 def test_library_exports_every_declared_enc_symbol(lib):
     header = (ROOT / "include" / "ce_enc.h").read_text()
-    declared = set(re.findall(r"^\s*(?:const\s+char\s*\*|int|void)\s+(ce_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.EXPORTS_ENC) == set(_lib.SIGNATURES_ENC), declared ^ set(_lib.EXPORTS_ENC)
-    for sym in declared:
-        fn = getattr(lib, sym)
-        restype, argtypes = _lib.SIGNATURES_ENC[sym]
-        assert fn.restype == restype and list(fn.argtypes) == argtypes, sym
-    others = (_lib.EXPORTS + _lib.EXPORTS_DENOISE + _lib.EXPORTS_DMRS + _lib.EXPORTS_EQ + _lib.EXPORTS_DEMOD + _lib.EXPORTS_RM
-              + _lib.EXPORTS_TP + _lib.EXPORTS_LDPC + _lib.EXPORTS_TB)
-    assert not declared & set(others) and lib.ce_abi_version() == 3 == _lib.CE_ABI_VERSION
-    for sym, (_, argtypes) in _lib.SIGNATURES_ENC.items():
-        proto = re.search(rf"\b{sym}\s*\(([^)]*)\)", header, flags=re.S).group(1)
-        assert len([a for a in proto.split(",") if a.strip()]) == len(argtypes), sym
+    # the header against the binding: tests/test_abi_conformance.py; here the sizes this stage's header implies, the
+    # package's re-export and what the header says of the NR-core form
     # LP64 sizes implied by the header: desc 10 * 4 + 3 pointers; info 6 * 4 + 8; view 44 * 4
     assert (C.sizeof(_lib.EncDesc), C.sizeof(_lib.EncInfo), C.sizeof(_lib.EncHostView)) == (64, 32, 176)
-    for struct, cls in (("ce_enc_desc", _lib.EncDesc), ("ce_enc_info", _lib.EncInfo), ("ce_enc_host_view", _lib.EncHostView)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = [re.sub(r"[\s*]|\[\d+\]", "", n) for decl in re.findall(r"(?:const\s+)?int(?:32|64)_t\s*\*?\s*([^;]+);", body) for n in decl.split(",")]
-        assert fields == [f[0] for f in cls._fields_], struct
-    for name in ("THREADS", "CORE_TRIANGULAR", "CORE_NR", "CRC_CHUNK"):
-        assert int(re.search(rf"#define CE_ENC_{name} (\d+)", header).group(1)) == getattr(_lib, "CE_ENC_" + name), name
-    assert "ce_enc.hip" in _lib.SOURCES and _lib.PUBLIC_HEADERS_ENC == ["ce_enc.h"] and "ce_enc.h" not in _lib.PUBLIC_HEADERS
+    assert "ce_enc.hip" in _lib.SOURCES and "ce_enc.h" in _lib.REGISTRY
     assert PKG.PuschTransportEncoder is EN.PuschTransportEncoder
     assert "THIS PROJECT'S READING" in header and "nothing is tested against them" in header      # the NR-core form is stated as this project's reading
 

@@ -2,8 +2,6 @@
 table and the row formula the kernel uses) against the plain-loop enumeration of tests/eq_oracle.py, descriptor errors
 before any device call, and the calibration of the tolerance rule the GPU tests apply.  No GPU."""
 import ctypes as C
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import pytest
 import eq_oracle as Q
 from srsran_ce_pytorch_amd import _lib, equalizer as EQ, synth as S
 
-ROOT = Path(__file__).resolve().parents[1]
 IDS = [c["name"] for c in Q.CASES]
 
 
@@ -22,16 +19,10 @@ def lib():
 
 
 def test_library_exports_every_declared_eq_symbol(lib):
-    header = (ROOT / "include" / "ce_eq.h").read_text()
-    declared = set(re.findall(r"^\s*(?:const\s+char\s*\*|int|void)\s+(ce_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.EXPORTS_EQ), declared ^ set(_lib.EXPORTS_EQ)
-    for sym in declared:
-        assert hasattr(lib, sym), sym
-    assert not declared & set(_lib.EXPORTS + _lib.EXPORTS_DENOISE + _lib.EXPORTS_DMRS) and lib.ce_abi_version() == 3
+    """The header against the binding: tests/test_abi_conformance.py.  Here: the sizes this stage's header implies."""
+    assert "ce_eq.h" in _lib.REGISTRY and "ce_eq.hip" in _lib.SOURCES
     # LP64 sizes implied by the header: hop 14 + 2 + 4*4 = 32; desc 6*4 + 2*32 = 88; info 4 + 4 + 8 = 16; view 4*14*4 + 4 = 228
     assert (C.sizeof(_lib.EqHopDesc), C.sizeof(_lib.EqDesc), C.sizeof(_lib.EqInfo), C.sizeof(_lib.EqHostView)) == (32, 88, 16, 228)
-    for name, val in (("CE_EQ_MAX_PORTS", _lib.CE_EQ_MAX_PORTS), ("CE_EQ_CHUNK_SC", _lib.CE_EQ_CHUNK_SC)):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == val
     assert EQ.CHUNK_SC == _lib.CE_EQ_CHUNK_SC and EQ.CHUNK_SC % 12 == 0
 
 

@@ -34,18 +34,13 @@ def _view(c, **kw):
 
 
 def test_library_exports_every_declared_mod_symbol(lib):
-    header = (ROOT / "include" / "ce_mod.h").read_text()
-    declared = set(re.findall(r"^\s*(?:const\s+char\s*\*|int|void)\s+(ce_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.EXPORTS_MOD), declared ^ set(_lib.EXPORTS_MOD)
-    for sym in declared:
-        assert hasattr(lib, sym), sym
-    assert "ce_mod.hip" in _lib.SOURCES and _lib.PUBLIC_HEADERS_MOD == ["ce_mod.h"] and lib.ce_abi_version() == 3
+    """The header against the binding: tests/test_abi_conformance.py.  Here: the sizes this stage's header implies and
+    its amplitudes against the oracles'."""
+    assert "ce_mod.hip" in _lib.SOURCES and "ce_mod.h" in _lib.REGISTRY
     # LP64 sizes implied by the header: hop 14 + 2*2 + 2 + 4*4 + 4 (pad) + 8 = 48; desc 8*4 + 2*48; info 6*4 + 8; view 6*4 + 5*14*4 + 12*4
     assert (C.sizeof(_lib.ModHopDesc), C.sizeof(_lib.ModDesc), C.sizeof(_lib.ModInfo), C.sizeof(_lib.ModHostView)) == (48, 128, 32, 352)
-    for name, val in (("CE_MOD_THREADS", _lib.CE_MOD_THREADS), ("CE_MOD_TILE_SC", _lib.CE_MOD_TILE_SC), ("CE_MOD_GROUP_SYMBOLS", _lib.CE_MOD_GROUP_SYMBOLS), ("CE_MOD_MAX_TILE_BLOCKS", _lib.CE_MOD_MAX_TILE_BLOCKS)):
-        assert re.search(rf"#define {name} {val}\b", header), name
-    for qm, name in ((2, "QPSK"), (4, "16QAM"), (6, "64QAM"), (8, "256QAM")):
-        assert re.search(rf"#define CE_MOD_A_{name} 0x{_lib.CE_MOD_A[qm]:08x}u", header), name
+    assert _lib.CE_MOD_A == {2: _lib.CE_MOD_A_QPSK, 4: _lib.CE_MOD_A_16QAM, 6: _lib.CE_MOD_A_64QAM, 8: _lib.CE_MOD_A_256QAM}
+    for qm in (2, 4, 6, 8):
         assert int(M.amplitude(qm).view(np.uint32)) == _lib.CE_MOD_A[qm]
     assert _lib.CE_MOD_A[2] == int(dmrs_oracle.A.view(np.uint32))            # QPSK's constant is the DM-RS amplitude
 
