@@ -173,6 +173,10 @@ CASES = [
     tb_case("c5_bytes", 2, 16976, C=5, which="24A", Kp=3424, P=3400),
     tb_case("c5_bits", 2, 16981, C=5, which="24A", Kp=3425, P=3401),                                 # every boundary at another bit offset
     tb_case("c152", 1, 1277992, slots=2, C=152, which="24A", Kp=8432, P=8408, B=1278016),            # the largest NR transport block
+    # three dwords per lane in one block, four in one block, four in each of two (appended: the seeds above keep their index)
+    tb_case("c1_piece3", 1, 4300, C=1, which="24A", Kp=4324, in_row_bytes=544),
+    tb_case("c1_piece4", 1, 7000, C=1, which="24A", Kp=7024, in_row_bytes=880),
+    tb_case("c2_piece4", 1, 13928, C=2, which="24A", Kp=7000, in_row_bytes=880),
 ]
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 SMALL_CASES = ["c1_tiny", "c1_8bit", "c1_odd", "c2_crc24_first", "c5_bits"]      # where assemble_loop is affordable

@@ -1,8 +1,8 @@
 """GPU tests of the transport-block assembly extension (include/ce_tb.h): the kernels against the integer oracle of
 tests/tb_oracle.py, by value (np.array_equal on tb, tb_status and cb_status -- no tolerance), on the pinned cases: one
 partly filled chunk, sizes that are no multiple of 8, the last CRC16 and the first CRC24A size, 66 chunks (two per lane),
-block boundaries at bit and at byte offsets into a dword, five blocks with every boundary at another offset, and the largest
-NR transport block (152 blocks).  The conditions the chain test leans on are asserted from the oracles alone in
+block boundaries at bit and at byte offsets into a dword, five blocks with every boundary at another offset, the largest
+NR transport block (152 blocks), and three and four dwords per lane in one block and in each of two.  The conditions the chain test leans on are asserted from the oracles alone in
 tests/test_tb.py.
 
 The file's name sorts it behind test_zzzzzz_hip_ldpc.py: every earlier GPU test keeps its place in the run."""
