@@ -106,6 +106,36 @@ int ce_tp_plan_get_info(const ce_tp_plan* plan, ce_tp_info* info);
 int ce_tp_deprecode(const ce_tp_plan* plan, const void* x_hat, const float* nvar, int64_t n_slots, void* x_out, float* nvar_out,
                     void* stream);
 
+/*
+ * Transform PRECODING, TS 38.211 6.3.1.4 itself (the transmit side: behind ce_mod_modulate), of n_slots slots in ONE
+ * launch on `stream`, with the plan of the same n_prbs and n_symbols: radix sequence, stride constants, twiddle table
+ * and launch geometry are the de-precoder's.  Asynchronous; n_slots == 0 launches nothing.  For slot b < n_slots,
+ * row r < S and k, i < M, complex64, strides and offsets in complex elements:
+ *     y[b y_slot_stride + y_row_offset[r] + k] = (1 / sqrt(M)) sum_i x[b x_slot_stride + x_row_offset[r] + i] exp(-j 2 pi i k / M)
+ * the sign and the scale of tests/tp_oracle.py `precode`.
+ *  x_row_offset, y_row_offset   host memory, S int32 each, read during the call (they travel in the kernel arguments);
+ *                               NULL = dense rows, r M.  With the rows of a resource grid [slot][n_sym][n_sc] (what
+ *                               ce_mod_modulate writes for one layer) the offset of the data symbol s is
+ *                               s n_sc + 12 prb_start and the slot stride n_sym n_sc.
+ * CE_ERR_INVALID unless: x and y are 16-byte aligned; both strides and every offset are even and >= 0 (every row then
+ * is 16-byte aligned, and every access to x and y is 16 bytes wide); offset + M <= slot stride for every row; the
+ * rows of one slot are pairwise disjoint, in x and in y; and x and y do not overlap -- except that y may be x itself
+ * with the identical stride and offsets, the in-place form (a grid is transformed where it lies).  The extent of a
+ * tensor is (n_slots - 1) stride + max offset + M elements.  In place is safe for the de-precoder's reason: a workgroup
+ * loads all of its rows before its first barrier, stores them after its last, and no other workgroup touches them.
+ * CE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups in one launch.
+ *
+ * float32 arithmetic (restated in tests/tpre_oracle.py `precode_f32`): the forward transform is the plan's inverse
+ * transform between two conjugations, DFT(x) = conj(IDFT(conj(x))).  The conjugation on load and the one on store flip
+ * a sign bit and are exact; between them run the de-precoder's Stockham passes over the same radix sequence with the same
+ * twiddles W[n] = exp(+j 2 pi n / M); the last pass scales by float32(1 / sqrt(M)), computed on the host in double and
+ * rounded once.  No reduction and no special-value handling: a NaN or an infinity in a row stays in that row and
+ * reaches no other.  No atomics, no scratch; every address comes from the block index, the thread index and host-derived
+ * values.  The pass moves 16 S M bytes per slot (x in, y out); ce_tp_info.bytes_per_slot keeps the de-precoder's 24 S M.
+ */
+int ce_tp_precode(const ce_tp_plan* plan, const void* x, int64_t x_slot_stride, const int32_t* x_row_offset, void* y,
+                  int64_t y_slot_stride, const int32_t* y_row_offset, int64_t n_slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

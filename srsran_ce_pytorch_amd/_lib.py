@@ -253,6 +253,7 @@ REGISTRY["ce_tp.h"] = Header(structs={"ce_tp_desc": TpDesc, "ce_tp_info": TpInfo
     "ce_tp_plan_destroy": (None, [_vp]),
     "ce_tp_plan_get_info": (_int, [_vp, _P(TpInfo)]),
     "ce_tp_deprecode": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ce_tp_precode": (_int, [_vp, _vp, _i64, _P(_i32), _vp, _i64, _P(_i32), _i64, _vp]),
 })
 CE_LDPC_MAX_ZC, CE_LDPC_MAX_ROWS, CE_LDPC_MAX_COLS, CE_LDPC_MAX_ROW_DEGREE = 384, 46, 68, 19
 CE_LDPC_L_BOUND, CE_LDPC_LDS_MAX, CE_LDPC_F32, CE_LDPC_I8 = 4497, 163840, 0, 1

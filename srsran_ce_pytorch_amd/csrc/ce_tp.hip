@@ -18,6 +18,10 @@
 //          pass has p = 0 (no twiddles), applies sqrt(M) / sum beta and leaves the row in natural order.
 //   store  16-byte stores of the row from LDS and of the broadcast nvar_out, contiguous over the lanes.
 // In place is safe: the stores come after the last barrier, the loads before the first.  DESIGN 6i.
+//
+// The forward transform (ce_tp_precode, the transmit side) is ce_tp_precode_kernel: the same launch geometry
+// and the same passes between a conjugating load and a conjugating store, rows at host-given offsets (dense rows, or
+// the data symbols of a resource grid), no weights and no sums.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -220,6 +224,71 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_kernel(TpDev P, const float2* __r
   }
 }
 
+// The row geometry of one ce_tp_precode call, by value in the kernel arguments; complex elements.
+struct TpRows {
+  int64_t x_slot, y_slot;            // slot strides
+  int32_t x_off[CE_MAX_SYMBOLS];     // row offsets inside a slot; entries >= S are 0
+  int32_t y_off[CE_MAX_SYMBOLS];
+  float scale;                       // float32(1 / sqrt(M))
+};
+
+// Transform precoding, DFT(x) = conj(IDFT(conj(x))): the passes above between a conjugating load and a conjugating store.
+__global__ __launch_bounds__(TP_NT) void ce_tp_precode_kernel(TpDev P, TpRows G, const float2* __restrict__ tw, const float4* x_in, float4* y_out) {
+  // x_in and y_out may be the same rows: no __restrict__; every load of the workgroup's rows comes before the first
+  // barrier, every store after the last
+  extern __shared__ float4 tp_lds[];
+  const uint32_t M = P.m, tpr = 1u << P.tpr_log2;
+  const uint32_t slot = blockIdx.x / P.wg_per_slot, wg = blockIdx.x - slot * P.wg_per_slot;
+  const uint32_t rl = threadIdx.x >> P.tpr_log2, lane = threadIdx.x & (tpr - 1u);   // row of the workgroup (wave-uniform), thread of the row
+  const uint32_t row = wg * P.rpw + rl;
+  const bool active = row < P.n_sym;   // the slot's last workgroup may hold fewer rows
+  const uint32_t ri = active ? row : 0u;
+  float2* buf0 = reinterpret_cast<float2*>(tp_lds) + (size_t)rl * 2u * M;
+  float2* buf1 = buf0 + M;
+  const uint32_t n_half = M >> 1;   // 16-byte pairs of REs
+
+  // ---- load: conj(x) into buf0 (an inactive row: zeros) ----
+  {
+    const float4* xr = x_in + (((int64_t)slot * G.x_slot + (int64_t)G.x_off[ri]) >> 1);   // strides and offsets are even
+    float4* u4 = reinterpret_cast<float4*>(buf0);
+    for (uint32_t h = lane; h < n_half; h += tpr) {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (active) v = xr[h];
+      u4[h] = make_float4(v.x, -v.y, v.z, -v.w);
+    }
+  }
+  __syncthreads();
+
+  // ---- passes ----
+  float2* src = buf0;
+  float2* dst = buf1;
+  uint32_t s = 1u;
+  for (uint32_t pass = 0; pass + 1u < P.n_passes; ++pass) {
+    const uint32_t r = P.radix[pass];
+    tp_pass_any<false>(r, src, dst, tw, M / r, s, P.magic[pass], lane, tpr, 1.0f);
+    s *= r;
+    __syncthreads();
+    float2* t = src;
+    src = dst;
+    dst = t;
+  }
+  {
+    const uint32_t r = P.radix[P.n_passes - 1u];
+    tp_pass_any<true>(r, src, dst, tw, s, s, 0u, lane, tpr, G.scale);   // M / r = s: the last radix closes the product
+    __syncthreads();
+  }
+
+  // ---- store: conj ----
+  if (active) {
+    const float4* res = reinterpret_cast<const float4*>(dst);
+    float4* yo = y_out + (((int64_t)slot * G.y_slot + (int64_t)G.y_off[ri]) >> 1);
+    for (uint32_t h = lane; h < n_half; h += tpr) {
+      const float4 v = res[h];
+      yo[h] = make_float4(v.x, -v.y, v.z, -v.w);
+    }
+  }
+}
+
 // ---- host derivation ----
 
 int tp_derive(const ce_tp_desc* d, ce_tp_host_view* v) {
@@ -349,4 +418,62 @@ extern "C" int ce_tp_deprecode(const ce_tp_plan* p, const void* x_hat, const flo
                      reinterpret_cast<const float4*>(x_hat), reinterpret_cast<const float4*>(nvar), reinterpret_cast<float4*>(x_out),
                      reinterpret_cast<float4*>(nvar_out));
   return ce_launch_status("transform de-precoding");
+}
+
+namespace {
+
+// The row geometry of one tensor of ce_tp_precode (`name` = "x" or "y"): offsets (NULL = dense rows) into `off`, the
+// largest into *max_off; CE_OK or the refusal.
+int tp_rows(const char* name, int M, int S, int64_t stride, const int32_t* offsets, int32_t* off, int32_t* max_off) {
+  if (stride < 0 || (stride & 1)) return ce_fail(CE_ERR_INVALID, "%s_slot_stride=%lld must be even and >= 0", name, (long long)stride);
+  *max_off = 0;
+  for (int r = 0; r < S; ++r) {
+    const int32_t o = offsets ? offsets[r] : r * M;
+    if (o < 0 || (o & 1)) return ce_fail(CE_ERR_INVALID, "%s_row_offset[%d]=%d must be even and >= 0", name, r, o);
+    if ((int64_t)o + M > stride) return ce_fail(CE_ERR_INVALID, "%s_row_offset[%d]=%d + M=%d exceeds %s_slot_stride=%lld", name, r, o, M, name, (long long)stride);
+    for (int q = 0; q < r; ++q)
+      if ((int64_t)o < (int64_t)off[q] + M && (int64_t)off[q] < (int64_t)o + M)
+        return ce_fail(CE_ERR_INVALID, "%s rows %d and %d overlap (offsets %d and %d, M=%d)", name, q, r, off[q], o, M);
+    off[r] = o;
+    if (o > *max_off) *max_off = o;
+  }
+  return CE_OK;
+}
+
+}  // namespace
+
+extern "C" int ce_tp_precode(const ce_tp_plan* p, const void* x, int64_t x_slot_stride, const int32_t* x_row_offset, void* y, int64_t y_slot_stride,
+                             const int32_t* y_row_offset, int64_t n_slots, void* stream) {
+  if (!p) return ce_fail(CE_ERR_INVALID, "null argument");
+  if (n_slots < 0) return ce_fail(CE_ERR_INVALID, "n_slots=%lld", (long long)n_slots);
+  if (n_slots == 0) return CE_OK;
+  if (!x || !y) return ce_fail(CE_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) return ce_fail(CE_ERR_INVALID, "x and y must be 16-byte aligned");
+  const int M = (int)p->dev.m, S = (int)p->dev.n_sym;
+  TpRows G{};
+  G.x_slot = x_slot_stride;
+  G.y_slot = y_slot_stride;
+  G.scale = (float)(1.0 / sqrt((double)M));
+  int32_t x_max = 0, y_max = 0;
+  if (const int rc = tp_rows("x", M, S, x_slot_stride, x_row_offset, G.x_off, &x_max); rc != CE_OK) return rc;
+  if (const int rc = tp_rows("y", M, S, y_slot_stride, y_row_offset, G.y_off, &y_max); rc != CE_OK) return rc;
+  const int64_t n_wg = n_slots * (int64_t)p->dev.wg_per_slot;
+  if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.wg_per_slot);
+  // n_slots < 2^31 here; the extents below, in bytes, must stay inside 64 bits
+  if (x_slot_stride > (INT64_MAX >> 4) / n_slots || y_slot_stride > (INT64_MAX >> 4) / n_slots)
+    return ce_fail(CE_ERR_INVALID, "slot strides %lld and %lld: the extent of %lld slots exceeds the address space", (long long)x_slot_stride, (long long)y_slot_stride, (long long)n_slots);
+  const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), y0 = reinterpret_cast<uintptr_t>(y);
+  if (x0 == y0) {
+    if (x_slot_stride != y_slot_stride || memcmp(G.x_off, G.y_off, sizeof(G.x_off)) != 0)
+      return ce_fail(CE_ERR_INVALID, "y is x with another stride or other row offsets: the in-place form needs the identical geometry");
+  } else {
+    const uintptr_t x1 = x0 + 8u * (uintptr_t)((n_slots - 1) * x_slot_stride + x_max + M);
+    const uintptr_t y1 = y0 + 8u * (uintptr_t)((n_slots - 1) * y_slot_stride + y_max + M);
+    if (x0 < y1 && y0 < x1) return ce_fail(CE_ERR_INVALID, "y overlaps x: only y = x with the identical stride and row offsets is an in-place form");
+  }
+  CeDeviceScope scope(p->device);
+  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
+  hipLaunchKernelGGL(ce_tp_precode_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->lds_bytes, (hipStream_t)stream, p->dev, G, p->tw,
+                     reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y));
+  return ce_launch_status("transform precoding");
 }

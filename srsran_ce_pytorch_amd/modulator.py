@@ -1,6 +1,7 @@
 """PUSCH modulator EXTENSION (include/ce_mod.h; the reference stops at the channel estimate): the forward counterpart of
 ``PuschDemapper`` and of the equalizer's data-RE walk in one stage -- scrambling, QAM and layer mapping, RE mapping and DM-RS
-insertion (TS 38.211 6.3.1.1 - 6.3.1.3, 6.3.1.6, 6.4.1.1.3, no transform precoding), one launch on the current stream.
+insertion (TS 38.211 6.3.1.1 - 6.3.1.3, 6.3.1.6, 6.4.1.1.3; transform precoding, 6.3.1.4, is ``PuschTransformPrecoder`` on
+the grid this stage returns), one launch on the current stream.
 
     eq = PuschEqualizer(hop1, hop2, L, n_prb_grid, reserved_re_mask=0x555)
     mod = PuschModulator.for_equalizer(eq, "16qam", scramble=True)        # same geometry, mask and device
