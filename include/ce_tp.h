@@ -1,7 +1,9 @@
 /*
  * ce_tp.h -- EXTENSION of libce_hip.so with NO counterpart in the reference: transform de-precoding (DFT-s-OFDM, the
  * inverse of TS 38.211 6.3.1.4) between ce_eq_equalize and ce_demod_demap, with the per-RE noise variances combined
- * into the per-symbol one the demapper needs.
+ * into the per-symbol one the demapper needs.  Behind it, further down: transform precoding, the forward direction
+ * (ce_tp_precode), and OFDM demodulation, samples to the resource grid (ce_ofdm_*), which runs the same passes over the
+ * same host view at the lengths 128 .. 4096.
  *
  * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
  * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
@@ -135,6 +137,70 @@ int ce_tp_deprecode(const ce_tp_plan* plan, const void* x_hat, const float* nvar
  */
 int ce_tp_precode(const ce_tp_plan* plan, const void* x, int64_t x_slot_stride, const int32_t* x_row_offset, void* y,
                   int64_t y_slot_stride, const int32_t* y_row_offset, int64_t n_slots, void* stream);
+
+/*
+ * OFDM DEMODULATION, the receive side in front of the estimator: time-domain I/Q samples of a slot to the resource grid
+ * received_rg -- cyclic-prefix removal, a DFT of length N = 2^n per symbol with the transforms' Stockham passes, the
+ * mapping of the bins onto the grid's subcarriers, compensation of the window advance and the per-symbol phase of
+ * TS 38.211 5.4.  The entry points take scalars and pointers only; the one structure is ce_tp_host_view, which describes
+ * an N-point transform as it stands: m_sc holds N, radix / stride_magic / threads_per_row / rows_per_workgroup / threads /
+ * lds_bytes / twiddle_bytes keep their meaning, and n_workgroups_per_slot counts the workgroups of one (slot, port).
+ *
+ * Plan values:
+ *     n_fft = N            128, 256, 512, 1024, 2048 or 4096
+ *     n_prb_grid           n_sc = 12 n_prb_grid <= N
+ *     n_sym                1 .. 14
+ *     cp_len[n_sym]        int32, samples, >= 0 (host memory, read during the call)
+ *     window_advance = a   0 <= a <= min cp_len: the DFT window starts a samples inside the cyclic prefix
+ *     sym_phasor           n_sym (re, im) float32 pairs phi_l, all finite (host memory), or NULL for none
+ * Derived: the slot length T = sum_l (cp_len[l] + N); the symbol start t_l = sum_{i<l} (cp_len[i] + N); the window start
+ * w_l = t_l + cp_len[l] - a; the signed bin of the grid subcarrier k < n_sc, q_k = k - n_sc / 2 (no k0 offset), at the
+ * transform's bin q_k mod N.  For slot b, port r, symbol l, with s = samples + b slot_stride + r port_stride:
+ *     Y[b][r][l][k] = phi_l exp(+j 2 pi q_k a / N) N^(-1/2) sum_{n<N} s[w_l + n] exp(-j 2 pi q_k n / N)
+ * The scale is unitary.  With a transmitter that puts X_k on bin q_k with the same scale and a channel shorter than
+ * min cp_len - a samples, Y = H_k X_k.
+ *
+ * float32 arithmetic (restated in tests/ofdm_oracle.py `demodulate_f32`): the forward transform is the inverse one between
+ * two conjugations, as in ce_tp_precode -- conjugate on load (exact), the Stockham passes over the radix sequence of the
+ * host view with the twiddles W[n] = exp(+j 2 pi n / N) computed in double and rounded once, the last pass scaling by
+ * float32(1 / sqrt(N)), conjugate on store (exact).  At the store the value v of bin q_k mod N is multiplied, in this
+ * order and each only where it applies, by
+ *     1. W[(q_k a) mod N]     where a != 0: a lookup in the plan's own twiddle table, the index in integer arithmetic
+ *     2. phi_l                where sym_phasor was given
+ * each a complex product (v.re w.re - v.im w.im, v.re w.im + v.im w.re).  With a = 0 and no phasors the result is the bare
+ * scaled DFT.  No reduction and no special-value handling: a NaN or an infinity in a window stays in that window's row.
+ *
+ *  samples   complex64 [slot][port][>= T], the last dimension contiguous; slot_stride and port_stride in complex
+ *            elements, any values >= 0 (a view into a longer capture; 0 repeats a row).  8-byte aligned, read with 8-byte
+ *            loads: cyclic prefixes such as 9 or 10 samples put windows at odd offsets.  Only the N samples of each of the
+ *            n_sym windows are read.
+ *  out       complex64 [slot][port][n_sym][n_sc], dense, 16-byte aligned, written with 16-byte stores, every element
+ *            exactly once: the estimator's fast layout, of which received_rg[B, R, n_sc, n_sym] is the permuted view.
+ * One launch on `stream`, asynchronous; n_slots == 0 or n_ports == 0 launches nothing.  One 256-thread workgroup handles
+ * rows_per_workgroup windows of one (slot, port); two LDS buffers of N complex64 per window.  No atomics, no scratch;
+ * every address comes from the block index, the thread index and host-derived values.
+ * CE_ERR_INVALID: n_fft not one of the six sizes; n_sc > N; n_sym outside 1..14; a negative cp_len; a outside
+ * 0 .. min cp_len; a non-finite phasor; a negative stride or count; strides whose extent exceeds the address space;
+ * samples not 8-byte or out not 16-byte aligned; out overlapping the extent
+ * (n_slots - 1) slot_stride + (n_ports - 1) port_stride + T of samples.
+ * CE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups in one launch.
+ */
+typedef struct ce_ofdm_plan ce_ofdm_plan; /* opaque */
+
+/* Host only: validation and derivation of ce_ofdm_plan_create without touching a GPU. */
+int ce_ofdm_derive_host(int32_t n_fft, int32_t n_prb_grid, int32_t n_sym, const int32_t* cp_len, int32_t window_advance,
+                        ce_tp_host_view* view);
+
+/* Host only: the plan's twiddle table W[n] = exp(+j 2 pi n / N), n < N, as N (re, im) float32 pairs into `twiddles`. */
+int ce_ofdm_copy_twiddles(int32_t n_fft, float* twiddles);
+
+/* Validates the values and uploads the twiddle table to `device`; abi_version = CE_ABI_VERSION. */
+int ce_ofdm_plan_create(int32_t abi_version, int32_t device, int32_t n_fft, int32_t n_prb_grid, int32_t n_sym, const int32_t* cp_len,
+                        int32_t window_advance, const float* sym_phasor, ce_ofdm_plan** out);
+void ce_ofdm_plan_destroy(ce_ofdm_plan* plan);
+
+int ce_ofdm_demodulate(const ce_ofdm_plan* plan, const void* samples, int64_t slot_stride, int64_t port_stride, int64_t n_slots,
+                       int64_t n_ports, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,11 @@ class Stage:
     def _build_desc(self, device_index: int):
         raise NotImplementedError
 
+    def _create(self, device_index: int, handle) -> int:
+        """The library's return code of plan creation into `handle`; a stage whose entry point takes no descriptor overrides it."""
+        desc = self._build_desc(device_index)                  # (and whatever host memory it points to) alive across the call
+        return getattr(self._lib, self._CREATE)(C.byref(desc), C.byref(handle))
+
     def _plan(self):
         if self._handle is None:
             device = self._device_arg
@@ -90,10 +95,9 @@ class Stage:
                 raise RuntimeError(f"{self._NOUN} runs on a ROCm GPU only (no CPU fallback)")
             if device.index is None:
                 device = torch.device("cuda", torch.cuda.current_device())
-            desc = self._build_desc(device.index)              # (and whatever host memory it points to) alive across the call
             handle = C.c_void_p()
             with torch.cuda.device(device):
-                rc = getattr(self._lib, self._CREATE)(C.byref(desc), C.byref(handle))
+                rc = self._create(device.index, handle)
             if rc != 0:
                 raise_for(rc)
             self._handle, self.device = handle, device

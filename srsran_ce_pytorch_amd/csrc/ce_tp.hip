@@ -10,12 +10,8 @@
 //          inside the wave (offsets 32 .. 1: a balanced tree, every lane ends with the same bits) and, for rows of two or
 //          four waves, (w0 + w1) + (w2 + w3) through LDS: the longest addition chain is
 //          4 ceil(M / 4 / threads_per_row) + log2(threads_per_row), and nothing depends on the batch.
-//   passes Stockham autosort, decimation in frequency, radix sequence r_0 r_1 .. from the host: at stride s (the product
-//          of the radices before) butterfly i < M / r reads src[i + k M / r], k < r, takes the r-point inverse DFT,
-//          multiplies output j by W[p j s] with p = floor(i / s) (one table of M twiddles for every pass, since the
-//          pass's own root of unity is W^s; p j s < M) and writes dst[(i - p s) + s (r p + j)].  The reads are contiguous
-//          over the lanes; the division is one v_mul_hi with a host-derived constant.  One barrier per pass.  The last
-//          pass has p = 0 (no twiddles), applies sqrt(M) / sum beta and leaves the row in natural order.
+//   passes the Stockham passes of ce_fft.h (shared with ce_ofdm.hip) over the host's radix sequence, one barrier per pass;
+//          the last pass applies sqrt(M) / sum beta and leaves the row in natural order.
 //   store  16-byte stores of the row from LDS and of the broadcast nvar_out, contiguous over the lanes.
 // In place is safe: the stores come after the last barrier, the loads before the first.  DESIGN 6i.
 //
@@ -30,12 +26,11 @@
 #include <memory>
 #include <vector>
 
+#include "ce_fft.h"
 #include "ce_stage.h"
 #include "ce_tp.h"
 
 namespace {
-
-constexpr int TP_NT = 256;
 
 struct TpDev {
   uint32_t m;            // M
@@ -48,80 +43,6 @@ struct TpDev {
   uint32_t magic[CE_TP_MAX_PASSES];
   float sqrt_m;          // float32(sqrt(M))
 };
-
-__device__ __forceinline__ float2 operator+(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 operator-(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 operator*(float c, float2 a) { return make_float2(c * a.x, c * a.y); }
-__device__ __forceinline__ float2 tp_cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-// a + j b and a - j b
-__device__ __forceinline__ float2 tp_add_j(float2 a, float2 b) { return make_float2(a.x - b.y, a.y + b.x); }
-__device__ __forceinline__ float2 tp_sub_j(float2 a, float2 b) { return make_float2(a.x + b.y, a.y - b.x); }
-
-// y_j = sum_k x_k exp(+j 2 pi j k / R)
-template <int R>
-__device__ __forceinline__ void tp_butterfly(const float2 (&x)[R], float2 (&y)[R]) {
-  if constexpr (R == 2) {
-    y[0] = x[0] + x[1];
-    y[1] = x[0] - x[1];
-  } else if constexpr (R == 4) {
-    const float2 t0 = x[0] + x[2], t1 = x[0] - x[2], t2 = x[1] + x[3], t3 = x[1] - x[3];
-    y[0] = t0 + t2;
-    y[1] = tp_add_j(t1, t3);
-    y[2] = t0 - t2;
-    y[3] = tp_sub_j(t1, t3);
-  } else if constexpr (R == 3) {
-    const float2 t = x[1] + x[2], u = x[1] - x[2];
-    const float2 m = x[0] - 0.5f * t, v = 0.8660254037844386f * u;
-    y[0] = x[0] + t;
-    y[1] = tp_add_j(m, v);
-    y[2] = tp_sub_j(m, v);
-  } else {
-    static_assert(R == 5, "radices 2, 3, 4 and 5");
-    constexpr float c1 = 0.30901699437494745f, c2 = -0.8090169943749475f, s1 = 0.9510565162951535f, s2 = 0.5877852522924731f;
-    const float2 t1 = x[1] + x[4], t2 = x[2] + x[3], u1 = x[1] - x[4], u2 = x[2] - x[3];
-    const float2 m1 = (x[0] + c1 * t1) + c2 * t2, m2 = (x[0] + c2 * t1) + c1 * t2;
-    const float2 n1 = s1 * u1 + s2 * u2, n2 = s2 * u1 - s1 * u2;
-    y[0] = (x[0] + t1) + t2;
-    y[1] = tp_add_j(m1, n1);
-    y[2] = tp_add_j(m2, n2);
-    y[3] = tp_sub_j(m2, n2);
-    y[4] = tp_sub_j(m1, n1);
-  }
-}
-
-// One pass over one row: `nb` = M / R butterflies at stride `s`; magic = floor(2^32 / s) + 1, or 0 where s = 1.
-template <int R, bool LAST>
-__device__ __forceinline__ void tp_pass(const float2* src, float2* dst, const float2* __restrict__ tw, uint32_t nb, uint32_t s, uint32_t magic,
-                                        uint32_t lane, uint32_t tpr, float scale) {
-  for (uint32_t i = lane; i < nb; i += tpr) {
-    float2 x[R], y[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) x[k] = src[i + k * nb];
-    tp_butterfly<R>(x, y);
-    if constexpr (LAST) {   // s = nb, p = 0: no twiddles, natural order
-#pragma unroll
-      for (int j = 0; j < R; ++j) dst[i + j * nb] = scale * y[j];
-    } else {
-      const uint32_t p = magic ? __umulhi(i, magic) : i;   // floor(i / s)
-      const uint32_t ps = p * s;
-      const uint32_t o = (i - ps) + ps * R;
-      dst[o] = y[0];
-#pragma unroll
-      for (int j = 1; j < R; ++j) dst[o + s * j] = tp_cmul(y[j], tw[ps * j]);
-    }
-  }
-}
-
-template <bool LAST>
-__device__ __forceinline__ void tp_pass_any(uint32_t r, const float2* src, float2* dst, const float2* __restrict__ tw, uint32_t nb, uint32_t s,
-                                            uint32_t magic, uint32_t lane, uint32_t tpr, float scale) {
-  switch (r) {   // uniform
-    case 4: tp_pass<4, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
-    case 2: tp_pass<2, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
-    case 3: tp_pass<3, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
-    default: tp_pass<5, LAST>(src, dst, tw, nb, s, magic, lane, tpr, scale); break;
-  }
-}
 
 // beta, gamma and u of one RE (include/ce_tp.h); an unusable RE is selected away, never multiplied
 __device__ __forceinline__ float2 tp_weigh(float xr, float xi, float nv, float& sb, float& sg) {
@@ -195,23 +116,7 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_kernel(TpDev P, const float2* __r
   const float nvo = any ? sg / sb : INFINITY;
 
   // ---- passes ----
-  float2* src = buf0;
-  float2* dst = buf1;
-  uint32_t s = 1u;
-  for (uint32_t pass = 0; pass + 1u < P.n_passes; ++pass) {
-    const uint32_t r = P.radix[pass];
-    tp_pass_any<false>(r, src, dst, tw, M / r, s, P.magic[pass], lane, tpr, 1.0f);
-    s *= r;
-    __syncthreads();
-    float2* t = src;
-    src = dst;
-    dst = t;
-  }
-  {
-    const uint32_t r = P.radix[P.n_passes - 1u];
-    tp_pass_any<true>(r, src, dst, tw, s, s, 0u, lane, tpr, scale);   // M / r = s: the last radix closes the product
-    __syncthreads();
-  }
+  const float2* dst = tp_passes(P, buf0, buf1, tw, lane, tpr, scale);
 
   // ---- store ----
   if (active) {
@@ -260,23 +165,7 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_precode_kernel(TpDev P, TpRows G,
   __syncthreads();
 
   // ---- passes ----
-  float2* src = buf0;
-  float2* dst = buf1;
-  uint32_t s = 1u;
-  for (uint32_t pass = 0; pass + 1u < P.n_passes; ++pass) {
-    const uint32_t r = P.radix[pass];
-    tp_pass_any<false>(r, src, dst, tw, M / r, s, P.magic[pass], lane, tpr, 1.0f);
-    s *= r;
-    __syncthreads();
-    float2* t = src;
-    src = dst;
-    dst = t;
-  }
-  {
-    const uint32_t r = P.radix[P.n_passes - 1u];
-    tp_pass_any<true>(r, src, dst, tw, s, s, 0u, lane, tpr, G.scale);   // M / r = s: the last radix closes the product
-    __syncthreads();
-  }
+  const float2* dst = tp_passes(P, buf0, buf1, tw, lane, tpr, G.scale);
 
   // ---- store: conj ----
   if (active) {
@@ -296,44 +185,9 @@ int tp_derive(const ce_tp_desc* d, ce_tp_host_view* v) {
   if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
   if (d->n_prbs < 1 || d->n_prbs > CE_TP_MAX_PRBS) return ce_fail(CE_ERR_INVALID, "n_prbs=%d outside 1..%d", d->n_prbs, CE_TP_MAX_PRBS);
   if (d->n_symbols < 1 || d->n_symbols > CE_MAX_SYMBOLS) return ce_fail(CE_ERR_INVALID, "n_symbols=%d outside 1..%d", d->n_symbols, CE_MAX_SYMBOLS);
-  int rest = d->n_prbs, e[3] = {2, 1, 0};   // exponents of 2, 3, 5 in M = 12 n_prbs
-  const int primes[3] = {2, 3, 5};
-  for (int i = 0; i < 3; ++i)
-    while (rest % primes[i] == 0) {
-      rest /= primes[i];
-      ++e[i];
-    }
-  if (rest != 1) return ce_fail(CE_ERR_INVALID, "n_prbs=%d has a prime factor above 5: transform precoding allocates 2^a 3^b 5^c PRBs", d->n_prbs);
-  const int M = 12 * d->n_prbs;
-  int n = 0;
-  for (int i = 0; i < e[0] / 2; ++i) v->radix[n++] = 4;
-  if (e[0] & 1) v->radix[n++] = 2;
-  for (int i = 0; i < e[1]; ++i) v->radix[n++] = 3;
-  for (int i = 0; i < e[2]; ++i) v->radix[n++] = 5;   // at most 7 entries for M <= 3300
-  v->n_passes = n;
-  uint32_t s = 1;
-  for (int i = 0; i < n; ++i) {
-    v->stride_magic[i] = s == 1 ? 0u : (uint32_t)(0x100000000ull / s) + 1u;   // exact for i s < 2^32 (i < M <= 3300, s <= M)
-    s *= (uint32_t)v->radix[i];
-  }
-  v->m_sc = M;
-  // a row's threads: about one radix-4 butterfly each in the small rows, where lanes would idle otherwise
-  v->threads_per_row = M <= 384 ? 64 : M <= 1152 ? 128 : 256;
-  v->threads = TP_NT;
-  v->rows_per_workgroup = TP_NT / v->threads_per_row;
-  v->lds_bytes = v->rows_per_workgroup * 2 * 8 * M;
-  v->twiddle_bytes = 8 * M;
-  v->n_workgroups_per_slot = (d->n_symbols + v->rows_per_workgroup - 1) / v->rows_per_workgroup;
+  if (!fft_derive(12 * d->n_prbs, d->n_symbols, v))
+    return ce_fail(CE_ERR_INVALID, "n_prbs=%d has a prime factor above 5: transform precoding allocates 2^a 3^b 5^c PRBs", d->n_prbs);
   return CE_OK;
-}
-
-void tp_twiddles(int M, float* out) {
-  const double two_pi = 6.283185307179586476925286766559;
-  for (int n = 0; n < M; ++n) {
-    const double a = two_pi * (double)n / (double)M;
-    out[2 * n] = (float)cos(a);
-    out[2 * n + 1] = (float)sin(a);
-  }
 }
 
 }  // namespace
@@ -355,7 +209,7 @@ extern "C" int ce_tp_copy_twiddles(const ce_tp_desc* d, float* twiddles) {
   if (!d || !twiddles) return ce_fail(CE_ERR_INVALID, "null argument");
   ce_tp_host_view v;
   if (const int rc = tp_derive(d, &v); rc != CE_OK) return rc;
-  tp_twiddles(v.m_sc, twiddles);
+  fft_twiddles(v.m_sc, twiddles);
   return CE_OK;
 }
 
@@ -383,7 +237,7 @@ extern "C" int ce_tp_plan_create(const ce_tp_desc* d, ce_tp_plan** out) {
   }
   D.sqrt_m = (float)sqrt((double)v.m_sc);
   std::vector<float> tw(2 * (size_t)v.m_sc);
-  tp_twiddles(v.m_sc, tw.data());
+  fft_twiddles(v.m_sc, tw.data());
   CeDeviceScope scope(d->device);
   const hipError_t e = ce_upload(scope.err, &p->tw, tw.data(), tw.size() * sizeof(float));
   if (e != hipSuccess) {
