@@ -1,7 +1,11 @@
-// What the row transforms (ce_tp.hip: transform de-precoding and precoding; ce_ofdm.hip: OFDM demodulation) share: the
-// Stockham passes of one row in LDS on the device, and on the host the radix sequence, stride constants, launch geometry
-// and twiddle table of a transform of any length 2^a 3^b 5^c.  Internal; everything here has internal linkage.
+// What the row transforms (ce_tp.hip: transform de-precoding and precoding; ce_ofdm.hip: OFDM demodulation) share: on the
+// device the row frame of a workgroup and the Stockham passes of one row in LDS, on the host the radix sequence, stride
+// constants, launch geometry and twiddle table of a transform of any length 2^a 3^b 5^c and the part of a plan that holds
+// them.  The loads and stores differ per kernel and stay there.  Internal; everything here has internal linkage.
 //
+//   frame  one 256-thread workgroup handles rows_per_workgroup rows of one item (a slot, or a (slot, port)),
+//          threads_per_row = 64, 128 or 256 threads each: whole waves, so everything that depends on the row is
+//          wave-uniform.  A row lives in two LDS buffers of M complex64 from the load to the store.
 //   passes Stockham autosort, decimation in frequency, radix sequence r_0 r_1 .. from the host: at stride s (the product
 //          of the radices before) butterfly i < M / r reads src[i + k M / r], k < r, takes the r-point inverse DFT,
 //          multiplies output j by W[p j s] with p = floor(i / s) (one table of M twiddles for every pass, since the
@@ -16,11 +20,41 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
+#include "ce_stage.h"
 #include "ce_tp.h"
 
 namespace {
 
 constexpr int TP_NT = 256;   // threads of a workgroup: 1, 2 or 4 rows of 256, 128 or 64 threads
+
+// The plan values of the frame and the passes: the first member of every kernel's own argument block.
+struct FftDev {
+  uint32_t m;             // transform length M (N in ce_ofdm.hip)
+  uint32_t n_rows;        // rows per item
+  uint32_t tpr_log2;      // log2(threads_per_row)
+  uint32_t rpw;           // rows per workgroup
+  uint32_t wg_per_item;   // workgroups per item
+  uint32_t n_passes;
+  uint32_t radix[CE_TP_MAX_PASSES];
+  uint32_t magic[CE_TP_MAX_PASSES];
+};
+
+// What a thread works on: row `row` of item `item` as thread `lane` of the row's `tpr`, between `buf0` and `buf1`.
+struct FftRow {
+  uint32_t item, row, lane, tpr;
+  bool active;   // row < n_rows: the item's last workgroup may hold fewer rows
+  float2 *buf0, *buf1;
+};
+
+// `lds`: the workgroup's dynamic LDS, rows_per_workgroup * 2 * M complex64.
+__device__ __forceinline__ FftRow fft_row(const FftDev& P, float4* lds) {
+  const uint32_t tpr = 1u << P.tpr_log2, item = blockIdx.x / P.wg_per_item, wg = blockIdx.x - item * P.wg_per_item;
+  const uint32_t rl = threadIdx.x >> P.tpr_log2, row = wg * P.rpw + rl;   // rl: row of the workgroup (wave-uniform)
+  float2* buf0 = reinterpret_cast<float2*>(lds) + (size_t)rl * 2u * P.m;
+  return {item, row, threadIdx.x & (tpr - 1u), tpr, row < P.n_rows, buf0, buf0 + P.m};
+}
 
 __device__ __forceinline__ float2 operator+(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 operator-(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
@@ -98,9 +132,8 @@ __device__ __forceinline__ void tp_pass_any(uint32_t r, const float2* src, float
 
 // Every pass of the workgroup's rows, the row in `buf0` (written before the workgroup's last barrier) with `buf1` as the
 // other half of the ping-pong pair; returns the buffer that holds the result, in natural order, after a barrier.
-// `P`: the kernel's plan values (m, n_passes, radix[], magic[]).  Every thread of the workgroup calls it.
-template <class Dev>
-__device__ __forceinline__ float2* tp_passes(const Dev& P, float2* buf0, float2* buf1, const float2* __restrict__ tw, uint32_t lane, uint32_t tpr,
+// Every thread of the workgroup calls it.
+__device__ __forceinline__ float2* tp_passes(const FftDev& P, float2* buf0, float2* buf1, const float2* __restrict__ tw, uint32_t lane, uint32_t tpr,
                                              float scale) {
   float2* src = buf0;
   float2* dst = buf1;
@@ -164,6 +197,48 @@ inline void fft_twiddles(int len, float* out) {
     out[2 * n] = (float)cos(a);
     out[2 * n + 1] = (float)sin(a);
   }
+}
+
+// The kernels' plan values of a derived view with `n_rows` rows per item.
+inline FftDev fft_dev(const ce_tp_host_view& v, int n_rows) {
+  FftDev D{};
+  D.m = (uint32_t)v.m_sc;
+  D.n_rows = (uint32_t)n_rows;
+  D.tpr_log2 = v.threads_per_row == 64 ? 6u : v.threads_per_row == 128 ? 7u : 8u;
+  D.rpw = (uint32_t)v.rows_per_workgroup;
+  D.wg_per_item = (uint32_t)v.n_workgroups_per_slot;
+  D.n_passes = (uint32_t)v.n_passes;
+  for (int i = 0; i < CE_TP_MAX_PASSES; ++i) {
+    D.radix[i] = (uint32_t)v.radix[i];
+    D.magic[i] = v.stride_magic[i];
+  }
+  return D;
+}
+
+// What a plan holds besides its kernel's argument block.
+struct FftPlan {
+  int device = 0;
+  int lds_bytes = 0;
+  float2* tw = nullptr;   // M twiddles on `device`
+};
+
+// *_plan_destroy of a plan that keeps its FftPlan in `core`.
+template <class Plan>
+void fft_plan_destroy(Plan* p) {
+  if (!p) return;
+  if (p->core.tw) (void)hipFree(p->core.tw);
+  delete p;
+}
+
+// Fills `c` for the view's transform on `device`: the twiddle table, generated and uploaded.  Whatever the result, c->tw
+// stays the plan's to free.
+inline hipError_t fft_plan_upload(FftPlan* c, int device, const ce_tp_host_view& v) {
+  c->device = device;
+  c->lds_bytes = v.lds_bytes;
+  std::vector<float> tw(2 * (size_t)v.m_sc);
+  fft_twiddles(v.m_sc, tw.data());
+  CeDeviceScope scope(device);
+  return ce_upload(scope.err, &c->tw, tw.data(), tw.size() * sizeof(float));
 }
 
 }  // namespace

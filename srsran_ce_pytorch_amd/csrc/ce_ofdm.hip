@@ -2,9 +2,8 @@
 // time-domain samples behind the cyclic prefix, its DFT of length N = 2^n scaled by 1 / sqrt(N), and the n_sc bins around
 // DC onto the subcarriers of the resource grid, with the window advance and the per-symbol phase compensated at the store.
 //
-// Kernel: one 256-thread workgroup handles rows_per_workgroup windows (symbols) of one (slot, port), threads_per_row = 64,
-// 128 or 256 threads each (whole waves, so everything that depends on the window is wave-uniform); a window lives in two
-// LDS buffers of N complex64 from the load to the store: 64 KiB at N = 4096, two workgroups per CU.
+// Kernel: the row frame of ce_fft.h, a row being a window (symbol) of one (slot, port): 64 KiB of LDS at N = 4096, two
+// workgroups per CU.
 //   load   thread t of the row takes the samples n = t, t + threads_per_row, .. of the window with 8-byte loads (a window
 //          may start at an odd sample), contiguous over the lanes, and writes conj(s_n) into buffer 0 in natural order.
 //          An inactive row of a (slot, port)'s last workgroup writes zeros.
@@ -22,7 +21,6 @@
 #include <string.h>
 
 #include <memory>
-#include <vector>
 
 #include "ce_fft.h"
 #include "ce_stage.h"
@@ -31,14 +29,7 @@
 namespace {
 
 struct OfdmDev {
-  uint32_t m;             // N
-  uint32_t n_sym;
-  uint32_t tpr_log2;      // log2(threads_per_row)
-  uint32_t rpw;           // rows (windows) per workgroup
-  uint32_t wg_per_item;   // workgroups per (slot, port)
-  uint32_t n_passes;
-  uint32_t radix[CE_TP_MAX_PASSES];
-  uint32_t magic[CE_TP_MAX_PASSES];
+  FftDev f;               // m = N, n_rows = n_sym; an item is a (slot, port)
   uint32_t n_sc;
   uint32_t adv;           // a
   uint32_t has_phasor;
@@ -50,15 +41,10 @@ struct OfdmDev {
 __global__ __launch_bounds__(TP_NT) void ce_ofdm_kernel(OfdmDev P, const float2* __restrict__ tw, const float2* __restrict__ samples, int64_t slot_stride,
                                                         int64_t port_stride, uint32_t n_ports, float4* __restrict__ out) {
   extern __shared__ float4 ofdm_lds[];
-  const uint32_t N = P.m, tpr = 1u << P.tpr_log2;
-  const uint32_t item = blockIdx.x / P.wg_per_item, wg = blockIdx.x - item * P.wg_per_item;   // item = slot n_ports + port
+  const auto [item, row, lane, tpr, active, buf0, buf1] = fft_row(P.f, ofdm_lds);   // item = slot n_ports + port
+  const uint32_t N = P.f.m;
   const uint32_t slot = item / n_ports, port = item - slot * n_ports;
-  const uint32_t rl = threadIdx.x >> P.tpr_log2, lane = threadIdx.x & (tpr - 1u);   // row of the workgroup (wave-uniform), thread of the row
-  const uint32_t row = wg * P.rpw + rl;
-  const bool active = row < P.n_sym;   // the (slot, port)'s last workgroup may hold fewer rows
   const uint32_t ri = active ? row : 0u;
-  float2* buf0 = reinterpret_cast<float2*>(ofdm_lds) + (size_t)rl * 2u * N;
-  float2* buf1 = buf0 + N;
 
   // ---- load: conj(s) into buf0 (an inactive row: zeros) ----
   {
@@ -71,13 +57,13 @@ __global__ __launch_bounds__(TP_NT) void ce_ofdm_kernel(OfdmDev P, const float2*
   }
   __syncthreads();
 
-  const float2* res = tp_passes(P, buf0, buf1, tw, lane, tpr, P.scale);
+  const float2* res = tp_passes(P.f, buf0, buf1, tw, lane, tpr, P.scale);
 
   // ---- store: conj, advance, phasor ----
   if (active) {
     const uint32_t n_half = P.n_sc >> 1, mask = N - 1u;
     const float2 phi = P.phasor[ri];
-    float4* o = out + ((((int64_t)item * P.n_sym + row) * (int64_t)P.n_sc) >> 1);
+    float4* o = out + ((((int64_t)item * P.f.n_rows + row) * (int64_t)P.n_sc) >> 1);
     for (uint32_t h = lane; h < n_half; h += tpr) {
       const uint32_t q = 2u * h - n_half;   // q_k of k = 2 h in two's complement: N divides 2^32, so `& mask` is mod N
       const float4 v = *reinterpret_cast<const float4*>(res + (q & mask));
@@ -128,11 +114,9 @@ int ofdm_derive(int32_t n_fft, int32_t n_prb_grid, int32_t n_sym, const int32_t*
 }  // namespace
 
 struct ce_ofdm_plan {
-  int device = 0;
+  FftPlan core;
   OfdmDev dev{};
-  int lds_bytes = 0;
   int32_t n_samples = 0;   // T
-  float2* tw = nullptr;
 };
 
 extern "C" int ce_ofdm_derive_host(int32_t n_fft, int32_t n_prb_grid, int32_t n_sym, const int32_t* cp_len, int32_t window_advance,
@@ -166,26 +150,12 @@ extern "C" int ce_ofdm_plan_create(int32_t abi_version, int32_t device, int32_t 
       if (!isfinite(sym_phasor[2 * l]) || !isfinite(sym_phasor[2 * l + 1])) return ce_fail(CE_ERR_INVALID, "sym_phasor[%d] is not finite", l);
       D.phasor[l] = make_float2(sym_phasor[2 * l], sym_phasor[2 * l + 1]);
     }
-  p->device = device;
-  p->lds_bytes = v.lds_bytes;
-  D.m = (uint32_t)n_fft;
-  D.n_sym = (uint32_t)n_sym;
-  D.tpr_log2 = v.threads_per_row == 64 ? 6u : v.threads_per_row == 128 ? 7u : 8u;
-  D.rpw = (uint32_t)v.rows_per_workgroup;
-  D.wg_per_item = (uint32_t)v.n_workgroups_per_slot;
-  D.n_passes = (uint32_t)v.n_passes;
-  for (int i = 0; i < CE_TP_MAX_PASSES; ++i) {
-    D.radix[i] = (uint32_t)v.radix[i];
-    D.magic[i] = v.stride_magic[i];
-  }
+  D.f = fft_dev(v, n_sym);
   D.n_sc = 12u * (uint32_t)n_prb_grid;
   D.adv = (uint32_t)window_advance;
   D.has_phasor = sym_phasor ? 1u : 0u;
   D.scale = (float)(1.0 / sqrt((double)n_fft));
-  std::vector<float> tw(2 * (size_t)n_fft);
-  fft_twiddles(n_fft, tw.data());
-  CeDeviceScope scope(device);
-  const hipError_t e = ce_upload(scope.err, &p->tw, tw.data(), tw.size() * sizeof(float));
+  const hipError_t e = fft_plan_upload(&p->core, device, v);
   if (e != hipSuccess) {
     ce_ofdm_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "OFDM demodulator plan upload: %s", hipGetErrorString(e));
@@ -194,11 +164,7 @@ extern "C" int ce_ofdm_plan_create(int32_t abi_version, int32_t device, int32_t 
   return CE_OK;
 }
 
-extern "C" void ce_ofdm_plan_destroy(ce_ofdm_plan* p) {
-  if (!p) return;
-  if (p->tw) (void)hipFree(p->tw);
-  delete p;
-}
+extern "C" void ce_ofdm_plan_destroy(ce_ofdm_plan* p) { fft_plan_destroy(p); }
 
 extern "C" int ce_ofdm_demodulate(const ce_ofdm_plan* p, const void* samples, int64_t slot_stride, int64_t port_stride, int64_t n_slots,
                                   int64_t n_ports, void* out, void* stream) {
@@ -212,10 +178,10 @@ extern "C" int ce_ofdm_demodulate(const ce_ofdm_plan* p, const void* samples, in
   if (reinterpret_cast<uintptr_t>(out) & 15u) return ce_fail(CE_ERR_INVALID, "out must be 16-byte aligned");
   const OfdmDev& D = p->dev;
   const int64_t lim = 0x7FFFFFFFll;
-  if (n_slots > lim || n_ports > lim || n_slots * n_ports > lim / (int64_t)D.wg_per_item)
+  if (n_slots > lim || n_ports > lim || n_slots * n_ports > lim / (int64_t)D.f.wg_per_item)
     return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots x %lld ports of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots,
-                   (long long)n_ports, D.wg_per_item);
-  const int64_t n_wg = n_slots * n_ports * (int64_t)D.wg_per_item;
+                   (long long)n_ports, D.f.wg_per_item);
+  const int64_t n_wg = n_slots * n_ports * (int64_t)D.f.wg_per_item;
   // n_slots, n_ports < 2^31 here; the extents below, in bytes, must stay inside 64 bits
   const int64_t room = INT64_MAX >> 6;
   if (slot_stride > room / n_slots || port_stride > room / n_ports)
@@ -223,11 +189,11 @@ extern "C" int ce_ofdm_demodulate(const ce_ofdm_plan* p, const void* samples, in
                    (long long)slot_stride, (long long)port_stride, (long long)n_slots, (long long)n_ports);
   const uintptr_t s0 = reinterpret_cast<uintptr_t>(samples), o0 = reinterpret_cast<uintptr_t>(out);
   const uintptr_t s1 = s0 + 8u * (uintptr_t)((n_slots - 1) * slot_stride + (n_ports - 1) * port_stride + p->n_samples);
-  const uintptr_t o1 = o0 + 8u * (uintptr_t)(n_slots * n_ports) * D.n_sym * D.n_sc;
+  const uintptr_t o1 = o0 + 8u * (uintptr_t)(n_slots * n_ports) * D.f.n_rows * D.n_sc;
   if (s0 < o1 && o0 < s1) return ce_fail(CE_ERR_INVALID, "out overlaps samples");
-  CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
-  hipLaunchKernelGGL(ce_ofdm_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->lds_bytes, (hipStream_t)stream, D, p->tw,
+  CeDeviceScope scope(p->core.device);
+  if (scope.err != hipSuccess) return ce_device_fail(p->core.device, scope.err);
+  hipLaunchKernelGGL(ce_ofdm_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->core.lds_bytes, (hipStream_t)stream, D, p->core.tw,
                      reinterpret_cast<const float2*>(samples), slot_stride, port_stride, (uint32_t)n_ports, reinterpret_cast<float4*>(out));
   return ce_launch_status("OFDM demodulation");
 }

@@ -1,9 +1,7 @@
 // EXTENSION (no reference counterpart, see include/ce_tp.h): transform de-precoding -- per data symbol the MMSE-weighted
 // inverse DFT of length M = 12 n_prbs of the equalizer's x_hat, and the per-symbol noise variance the demapper needs.
 //
-// Kernel: one 256-thread workgroup handles rows_per_workgroup rows (data symbols) of one slot, threads_per_row = 64, 128
-// or 256 threads each (whole waves, so everything that depends on the row is wave-uniform); a row lives in two
-// LDS buffers of M complex64 from the load to the store.
+// Kernel: the row frame of ce_fft.h, a row being a data symbol of one slot.
 //   load   thread t of the row takes the groups g = t, t + threads_per_row, .. of 4 REs (two 16-byte loads of x_hat,
 //          one of nvar), forms u_k, beta_k, gamma_k, adds beta and gamma to its own two partial sums in ascending k and
 //          writes u into buffer 0 in natural order.  The partial sums are reduced by a butterfly of lane exchanges
@@ -24,7 +22,6 @@
 #include <string.h>
 
 #include <memory>
-#include <vector>
 
 #include "ce_fft.h"
 #include "ce_stage.h"
@@ -33,15 +30,8 @@
 namespace {
 
 struct TpDev {
-  uint32_t m;            // M
-  uint32_t n_sym;        // S
-  uint32_t tpr_log2;     // log2(threads_per_row)
-  uint32_t rpw;          // rows per workgroup
-  uint32_t wg_per_slot;  // workgroups per slot
-  uint32_t n_passes;
-  uint32_t radix[CE_TP_MAX_PASSES];
-  uint32_t magic[CE_TP_MAX_PASSES];
-  float sqrt_m;          // float32(sqrt(M))
+  FftDev f;       // m = M, n_rows = S; an item is a slot
+  float sqrt_m;   // float32(sqrt(M))
 };
 
 // beta, gamma and u of one RE (include/ce_tp.h); an unusable RE is selected away, never multiplied
@@ -61,14 +51,9 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_kernel(TpDev P, const float2* __r
   // before the first barrier, every store after the last
   extern __shared__ float4 tp_lds[];
   __shared__ float red[TP_NT / 64][2];
-  const uint32_t M = P.m, tpr = 1u << P.tpr_log2;
-  const uint32_t slot = blockIdx.x / P.wg_per_slot, wg = blockIdx.x - slot * P.wg_per_slot;
-  const uint32_t rl = threadIdx.x >> P.tpr_log2, lane = threadIdx.x & (tpr - 1u);   // row of the workgroup (wave-uniform), thread of the row
-  const uint32_t row = wg * P.rpw + rl;
-  const bool active = row < P.n_sym;   // the slot's last workgroup may hold fewer rows
-  const int64_t grow = (int64_t)slot * P.n_sym + row;
-  float2* buf0 = reinterpret_cast<float2*>(tp_lds) + (size_t)rl * 2u * M;
-  float2* buf1 = buf0 + M;
+  const auto [slot, row, lane, tpr, active, buf0, buf1] = fft_row(P.f, tp_lds);
+  const uint32_t M = P.f.m;
+  const int64_t grow = (int64_t)slot * P.f.n_rows + row;
   const uint32_t n_grp = M >> 2;   // groups of 4 REs
 
   // ---- load: u into buf0, the two sums ----
@@ -103,11 +88,11 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_kernel(TpDev P, const float2* __r
     red[wave][1] = sg;
   }
   __syncthreads();
-  if (P.tpr_log2 == 7u) {
+  if (P.f.tpr_log2 == 7u) {
     const uint32_t w0 = wave & ~1u;
     sb = red[w0][0] + red[w0 + 1u][0];
     sg = red[w0][1] + red[w0 + 1u][1];
-  } else if (P.tpr_log2 == 8u) {
+  } else if (P.f.tpr_log2 == 8u) {
     sb = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
     sg = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
   }
@@ -116,7 +101,7 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_kernel(TpDev P, const float2* __r
   const float nvo = any ? sg / sb : INFINITY;
 
   // ---- passes ----
-  const float2* dst = tp_passes(P, buf0, buf1, tw, lane, tpr, scale);
+  const float2* dst = tp_passes(P.f, buf0, buf1, tw, lane, tpr, scale);
 
   // ---- store ----
   if (active) {
@@ -142,15 +127,9 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_precode_kernel(TpDev P, TpRows G,
   // x_in and y_out may be the same rows: no __restrict__; every load of the workgroup's rows comes before the first
   // barrier, every store after the last
   extern __shared__ float4 tp_lds[];
-  const uint32_t M = P.m, tpr = 1u << P.tpr_log2;
-  const uint32_t slot = blockIdx.x / P.wg_per_slot, wg = blockIdx.x - slot * P.wg_per_slot;
-  const uint32_t rl = threadIdx.x >> P.tpr_log2, lane = threadIdx.x & (tpr - 1u);   // row of the workgroup (wave-uniform), thread of the row
-  const uint32_t row = wg * P.rpw + rl;
-  const bool active = row < P.n_sym;   // the slot's last workgroup may hold fewer rows
+  const auto [slot, row, lane, tpr, active, buf0, buf1] = fft_row(P.f, tp_lds);
   const uint32_t ri = active ? row : 0u;
-  float2* buf0 = reinterpret_cast<float2*>(tp_lds) + (size_t)rl * 2u * M;
-  float2* buf1 = buf0 + M;
-  const uint32_t n_half = M >> 1;   // 16-byte pairs of REs
+  const uint32_t n_half = P.f.m >> 1;   // 16-byte pairs of REs
 
   // ---- load: conj(x) into buf0 (an inactive row: zeros) ----
   {
@@ -165,7 +144,7 @@ __global__ __launch_bounds__(TP_NT) void ce_tp_precode_kernel(TpDev P, TpRows G,
   __syncthreads();
 
   // ---- passes ----
-  const float2* dst = tp_passes(P, buf0, buf1, tw, lane, tpr, G.scale);
+  const float2* dst = tp_passes(P.f, buf0, buf1, tw, lane, tpr, G.scale);
 
   // ---- store: conj ----
   if (active) {
@@ -193,11 +172,9 @@ int tp_derive(const ce_tp_desc* d, ce_tp_host_view* v) {
 }  // namespace
 
 struct ce_tp_plan {
-  int device = 0;
+  FftPlan core;
   ce_tp_info info{};
   TpDev dev{};
-  int lds_bytes = 0;
-  float2* tw = nullptr;
 };
 
 extern "C" int ce_tp_derive_host(const ce_tp_desc* d, ce_tp_host_view* v) {
@@ -219,27 +196,12 @@ extern "C" int ce_tp_plan_create(const ce_tp_desc* d, ce_tp_plan** out) {
   if (const int rc = tp_derive(d, &v); rc != CE_OK) return rc;
   auto p = ce_new_plan<ce_tp_plan>();
   if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
-  p->device = d->device;
   p->info.m_sc = v.m_sc;
   p->info.n_symbols = d->n_symbols;
   p->info.bytes_per_slot = (int64_t)d->n_symbols * v.m_sc * 24;
-  p->lds_bytes = v.lds_bytes;
-  TpDev& D = p->dev;
-  D.m = (uint32_t)v.m_sc;
-  D.n_sym = (uint32_t)d->n_symbols;
-  D.tpr_log2 = v.threads_per_row == 64 ? 6u : v.threads_per_row == 128 ? 7u : 8u;
-  D.rpw = (uint32_t)v.rows_per_workgroup;
-  D.wg_per_slot = (uint32_t)v.n_workgroups_per_slot;
-  D.n_passes = (uint32_t)v.n_passes;
-  for (int i = 0; i < CE_TP_MAX_PASSES; ++i) {
-    D.radix[i] = (uint32_t)v.radix[i];
-    D.magic[i] = v.stride_magic[i];
-  }
-  D.sqrt_m = (float)sqrt((double)v.m_sc);
-  std::vector<float> tw(2 * (size_t)v.m_sc);
-  fft_twiddles(v.m_sc, tw.data());
-  CeDeviceScope scope(d->device);
-  const hipError_t e = ce_upload(scope.err, &p->tw, tw.data(), tw.size() * sizeof(float));
+  p->dev.f = fft_dev(v, d->n_symbols);
+  p->dev.sqrt_m = (float)sqrt((double)v.m_sc);
+  const hipError_t e = fft_plan_upload(&p->core, d->device, v);
   if (e != hipSuccess) {
     ce_tp_plan_destroy(p.release());
     return ce_fail(CE_ERR_HIP, "de-precoder plan upload: %s", hipGetErrorString(e));
@@ -248,11 +210,7 @@ extern "C" int ce_tp_plan_create(const ce_tp_desc* d, ce_tp_plan** out) {
   return CE_OK;
 }
 
-extern "C" void ce_tp_plan_destroy(ce_tp_plan* p) {
-  if (!p) return;
-  if (p->tw) (void)hipFree(p->tw);
-  delete p;
-}
+extern "C" void ce_tp_plan_destroy(ce_tp_plan* p) { fft_plan_destroy(p); }
 
 extern "C" int ce_tp_plan_get_info(const ce_tp_plan* p, ce_tp_info* info) { return ce_get_info(p, info); }
 
@@ -264,11 +222,11 @@ extern "C" int ce_tp_deprecode(const ce_tp_plan* p, const void* x_hat, const flo
   if (!x_hat || !nvar || !x_out || !nvar_out) return ce_fail(CE_ERR_INVALID, "null argument");
   if ((reinterpret_cast<uintptr_t>(x_hat) | reinterpret_cast<uintptr_t>(nvar) | reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(nvar_out)) & 15u)
     return ce_fail(CE_ERR_INVALID, "x_hat, nvar, x_out and nvar_out must be 16-byte aligned");
-  const int64_t n_wg = n_slots * (int64_t)p->dev.wg_per_slot;
-  if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.wg_per_slot);
-  CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
-  hipLaunchKernelGGL(ce_tp_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->lds_bytes, (hipStream_t)stream, p->dev, p->tw,
+  const int64_t n_wg = n_slots * (int64_t)p->dev.f.wg_per_item;
+  if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.f.wg_per_item);
+  CeDeviceScope scope(p->core.device);
+  if (scope.err != hipSuccess) return ce_device_fail(p->core.device, scope.err);
+  hipLaunchKernelGGL(ce_tp_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->core.lds_bytes, (hipStream_t)stream, p->dev, p->core.tw,
                      reinterpret_cast<const float4*>(x_hat), reinterpret_cast<const float4*>(nvar), reinterpret_cast<float4*>(x_out),
                      reinterpret_cast<float4*>(nvar_out));
   return ce_launch_status("transform de-precoding");
@@ -303,7 +261,7 @@ extern "C" int ce_tp_precode(const ce_tp_plan* p, const void* x, int64_t x_slot_
   if (n_slots == 0) return CE_OK;
   if (!x || !y) return ce_fail(CE_ERR_INVALID, "null argument");
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) return ce_fail(CE_ERR_INVALID, "x and y must be 16-byte aligned");
-  const int M = (int)p->dev.m, S = (int)p->dev.n_sym;
+  const int M = (int)p->dev.f.m, S = (int)p->dev.f.n_rows;
   TpRows G{};
   G.x_slot = x_slot_stride;
   G.y_slot = y_slot_stride;
@@ -311,8 +269,8 @@ extern "C" int ce_tp_precode(const ce_tp_plan* p, const void* x, int64_t x_slot_
   int32_t x_max = 0, y_max = 0;
   if (const int rc = tp_rows("x", M, S, x_slot_stride, x_row_offset, G.x_off, &x_max); rc != CE_OK) return rc;
   if (const int rc = tp_rows("y", M, S, y_slot_stride, y_row_offset, G.y_off, &y_max); rc != CE_OK) return rc;
-  const int64_t n_wg = n_slots * (int64_t)p->dev.wg_per_slot;
-  if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.wg_per_slot);
+  const int64_t n_wg = n_slots * (int64_t)p->dev.f.wg_per_item;
+  if (n_wg > 0x7FFFFFFFll) return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots, p->dev.f.wg_per_item);
   // n_slots < 2^31 here; the extents below, in bytes, must stay inside 64 bits
   if (x_slot_stride > (INT64_MAX >> 4) / n_slots || y_slot_stride > (INT64_MAX >> 4) / n_slots)
     return ce_fail(CE_ERR_INVALID, "slot strides %lld and %lld: the extent of %lld slots exceeds the address space", (long long)x_slot_stride, (long long)y_slot_stride, (long long)n_slots);
@@ -325,9 +283,9 @@ extern "C" int ce_tp_precode(const ce_tp_plan* p, const void* x, int64_t x_slot_
     const uintptr_t y1 = y0 + 8u * (uintptr_t)((n_slots - 1) * y_slot_stride + y_max + M);
     if (x0 < y1 && y0 < x1) return ce_fail(CE_ERR_INVALID, "y overlaps x: only y = x with the identical stride and row offsets is an in-place form");
   }
-  CeDeviceScope scope(p->device);
-  if (scope.err != hipSuccess) return ce_device_fail(p->device, scope.err);
-  hipLaunchKernelGGL(ce_tp_precode_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->lds_bytes, (hipStream_t)stream, p->dev, G, p->tw,
+  CeDeviceScope scope(p->core.device);
+  if (scope.err != hipSuccess) return ce_device_fail(p->core.device, scope.err);
+  hipLaunchKernelGGL(ce_tp_precode_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->core.lds_bytes, (hipStream_t)stream, p->dev, G, p->core.tw,
                      reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y));
   return ce_launch_status("transform precoding");
 }

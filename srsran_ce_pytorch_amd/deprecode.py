@@ -41,6 +41,30 @@ def twiddles(n_prbs: int, n_symbols: int = 1) -> np.ndarray:
     return w
 
 
+def _copy_geometry(stage, view) -> None:
+    """The launch geometry a row-transform stage shows as attributes, from its host view."""
+    stage.radix = tuple(int(r) for r in view.radix[:view.n_passes])
+    stage.rows_per_workgroup, stage.threads_per_row = int(view.rows_per_workgroup), int(view.threads_per_row)
+
+
+def _data_symbols(view, n_sym: int) -> list:
+    """The symbols with data of an equalizer's or a modulator's host view; ``ValueError`` unless each has it on all 12 REs."""
+    syms = [s for s in range(n_sym) if view.sym_hop[s] >= 0 and view.data_res_per_prb[s] != 0]
+    for s in syms:
+        if view.data_res_per_prb[s] != 12:
+            raise ValueError(f"symbol {s} carries data on {view.data_res_per_prb[s]} of 12 REs per PRB: transform precoding "
+                             "needs DM-RS symbols without data (reserved_re_mask = 0xFFF)")
+    return syms
+
+
+def _check_dense_rows(name: str, t, dtype, n: int, dev) -> None:
+    """``ValueError`` unless ``t`` is a dense ``dtype`` tensor ``[slots, n]`` or ``[slots, n, 1]`` on ``dev``."""
+    if not isinstance(t, torch.Tensor) or t.device != dev:
+        raise ValueError(f"{name} must be a tensor on {dev}")
+    if t.dtype != dtype or not t.is_contiguous() or t.dim() not in (2, 3) or tuple(t.shape[1:]) not in ((n,), (n, 1)):
+        raise ValueError(f"{name} must be a dense {dtype} tensor [slots, {n}] or [slots, {n}, 1], got {t.dtype} {tuple(t.shape)}")
+
+
 class PuschTransformDeprecoder(_stage.Stage):
     _CREATE, _DESTROY, _LAUNCH = "ce_tp_plan_create", "ce_tp_plan_destroy", "ce_tp_deprecode"
     _NOUN = "the transform de-precoder"
@@ -50,8 +74,7 @@ class PuschTransformDeprecoder(_stage.Stage):
         self._args = (int(n_prbs), int(n_symbols))
         view = derive_host(*self._args)
         self.n_prbs, self.n_symbols, self.m_sc = int(n_prbs), int(n_symbols), int(view.m_sc)
-        self.radix = tuple(int(r) for r in view.radix[:view.n_passes])
-        self.rows_per_workgroup, self.threads_per_row = int(view.rows_per_workgroup), int(view.threads_per_row)
+        _copy_geometry(self, view)
 
     @classmethod
     def for_equalizer(cls, eq, device=None) -> "PuschTransformDeprecoder":
@@ -60,19 +83,10 @@ class PuschTransformDeprecoder(_stage.Stage):
         ``n_prbs``."""
         if eq.n_layers != 1:
             raise ValueError(f"transform precoding is single-layer, the equalizer has {eq.n_layers} layers")
-        desc, view = eq._desc, eq._view
-        widths = {int(desc.hop[h].n_prbs) for h in range(desc.n_hops)}
+        widths = {int(eq._desc.hop[h].n_prbs) for h in range(eq._desc.n_hops)}
         if len(widths) != 1:
             raise ValueError(f"the hops have {sorted(widths)} PRBs: transform precoding needs one width")
-        n_prbs, n_symbols = widths.pop(), 0
-        for s in range(eq.n_sym):
-            if view.sym_hop[s] < 0 or view.data_res_per_prb[s] == 0:
-                continue
-            if view.data_res_per_prb[s] != 12:
-                raise ValueError(f"symbol {s} carries data on {view.data_res_per_prb[s]} of 12 REs per PRB: transform precoding "
-                                 "needs DM-RS symbols without data (reserved_re_mask = 0xFFF)")
-            n_symbols += 1
-        return cls(n_prbs, n_symbols, device=device if device is not None else eq._device_arg)
+        return cls(widths.pop(), len(_data_symbols(eq._view, eq.n_sym)), device=device if device is not None else eq._device_arg)
 
     def _build_desc(self, device_index: int):
         return build_desc(*self._args, device_index=device_index)
@@ -86,11 +100,8 @@ class PuschTransformDeprecoder(_stage.Stage):
         self._plan()
         dev = self.device
         n = self.n_symbols * self.m_sc
-        for name, t, dt in (("x_hat", x_hat, torch.complex64), ("nvar", nvar, torch.float32)):
-            if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError(f"{name} must be a tensor on {dev}")
-            if t.dtype != dt or not t.is_contiguous() or t.dim() not in (2, 3) or tuple(t.shape[1:]) not in ((n,), (n, 1)):
-                raise ValueError(f"{name} must be a dense {dt} tensor [slots, {n}] or [slots, {n}, 1], got {t.dtype} {tuple(t.shape)}")
+        _check_dense_rows("x_hat", x_hat, torch.complex64, n, dev)
+        _check_dense_rows("nvar", nvar, torch.float32, n, dev)
         B = x_hat.shape[0]
         if nvar.shape[0] != B:
             raise ValueError(f"x_hat holds {B} slots, nvar {nvar.shape[0]}")

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, _stage
+from . import _lib, _stage, deprecode
 
 FFT_SIZES = (128, 256, 512, 1024, 2048, 4096)
 
@@ -102,8 +102,7 @@ class PuschOfdmDemodulator(_stage.Stage):
         view = derive_host(self.n_fft, self.n_prb_grid, cp_len, self.n_sym, self.window_advance)
         self.cp_len = tuple(int(c) for c in cp_len)
         self.n_sc, self.n_samples = 12 * self.n_prb_grid, sum(self.cp_len) + self.n_sym * self.n_fft
-        self.radix = tuple(int(r) for r in view.radix[:view.n_passes])
-        self.rows_per_workgroup, self.threads_per_row = int(view.rows_per_workgroup), int(view.threads_per_row)
+        deprecode._copy_geometry(self, view)
         self.sym_phasor = None
         if sym_phasor is not None:
             phi = np.asarray(sym_phasor.cpu() if isinstance(sym_phasor, torch.Tensor) else sym_phasor)

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _stage
 from . import modulator as _mod
-from .deprecode import build_desc, derive_host
+from .deprecode import _check_dense_rows, _copy_geometry, _data_symbols, build_desc, derive_host
 
 
 class PuschTransformPrecoder(_stage.Stage):
@@ -33,8 +33,7 @@ class PuschTransformPrecoder(_stage.Stage):
         self._args = (int(n_prbs), int(n_symbols))
         view = derive_host(*self._args)
         self.n_prbs, self.n_symbols, self.m_sc = int(n_prbs), int(n_symbols), int(view.m_sc)
-        self.radix = tuple(int(r) for r in view.radix[:view.n_passes])
-        self.rows_per_workgroup, self.threads_per_row = int(view.rows_per_workgroup), int(view.threads_per_row)
+        _copy_geometry(self, view)
         self.row_offsets, self.slot_stride, self._grid_shape = None, None, None      # set by for_modulator
 
     @classmethod
@@ -52,14 +51,7 @@ class PuschTransformPrecoder(_stage.Stage):
         n_prbs = int(desc.hop[0].n_prbs)                         # (the modulator refuses hops of unequal width)
         starts = [int(desc.hop[h].prb_start) for h in range(desc.n_hops)]
         del keep
-        offsets = []
-        for s in range(mod.n_sym):
-            if view.sym_hop[s] < 0 or view.data_res_per_prb[s] == 0:
-                continue
-            if view.data_res_per_prb[s] != 12:
-                raise ValueError(f"symbol {s} carries data on {view.data_res_per_prb[s]} of 12 REs per PRB: transform precoding "
-                                 "needs DM-RS symbols without data (reserved_re_mask = 0xFFF)")
-            offsets.append(s * mod.n_sc + 12 * starts[view.sym_hop[s]])
+        offsets = [s * mod.n_sc + 12 * starts[view.sym_hop[s]] for s in _data_symbols(view, mod.n_sym)]
         pre = cls(n_prbs, len(offsets), device=device if device is not None else mod._device_arg)
         pre.row_offsets, pre.slot_stride, pre._grid_shape = tuple(offsets), mod.n_sym * mod.n_sc, (mod.n_sc, mod.n_sym)
         return pre
@@ -74,10 +66,7 @@ class PuschTransformPrecoder(_stage.Stage):
         self._plan()
         dev = self.device
         n = self.n_symbols * self.m_sc
-        if not isinstance(x, torch.Tensor) or x.device != dev:
-            raise ValueError(f"x must be a tensor on {dev}")
-        if x.dtype != torch.complex64 or not x.is_contiguous() or x.dim() not in (2, 3) or tuple(x.shape[1:]) not in ((n,), (n, 1)):
-            raise ValueError(f"x must be a dense {torch.complex64} tensor [slots, {n}] or [slots, {n}, 1], got {x.dtype} {tuple(x.shape)}")
+        _check_dense_rows("x", x, torch.complex64, n, dev)
         B = x.shape[0]
         shape = (B, n)
         if out is None:

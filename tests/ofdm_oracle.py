@@ -5,7 +5,7 @@ and the tolerance rule they follow.
 (unitary) with grid subcarrier k on the signed bin q_k = k - n_sc / 2, and the cyclic prefix in front.  `demodulate_ref`
 is the operator of include/ce_tp.h in float64 (`np.fft.fft`, or a literal N x N DFT matrix up to N = 512, so that the
 sign and the scale do not lean on a library's convention).  `demodulate_f32` restates the kernel's own float32
-arithmetic -- `tpre_oracle.precode_f32` (conjugate, the passes of `tp_oracle._butterfly_f32` over the radix sequence and
+arithmetic -- `tpre_oracle.precode_f32` (conjugate, the passes of `tp_oracle.passes_f32` over the radix sequence and
 the twiddle table of the library's host entry points, float32(1 / sqrt(N)) in the last pass, conjugate), then at the
 store the product with W[(q_k a) mod N] where a != 0 and the product with phi_l where phasors are given, in that order --
 only to calibrate the tolerance.

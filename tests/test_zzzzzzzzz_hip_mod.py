@@ -15,12 +15,10 @@ import numpy as np
 import pytest
 import torch
 
-import enc_oracle as E
 import eq_oracle as Q
+import loop_chain
 import mod_oracle as M
-import tb_oracle as T
-from srsran_ce_pytorch_amd import _lib, demod as DM, dmrs as DR, encoder as EN, equalizer as EQ, estimator as ES, ldpc as LD, modulator as MO
-from srsran_ce_pytorch_amd import ratematch as RM, synth as S, transportblock as TB
+from srsran_ce_pytorch_amd import _lib, demod as DM, equalizer as EQ, modulator as MO
 
 pytestmark = pytest.mark.gpu
 
@@ -262,39 +260,14 @@ def test_the_loop_through_every_stage_returns_the_transport_block(name):
     PuschTransportBlock: the transport block sent comes back with tb_status 0; a slot whose rnti differs between modulator
     and demapper fails its CRC."""
     dev = _dev()
-    c, lp, gr, case = E.CASE_BY_NAME[name], E.LOOPS[name], E.graph(name), M.loop_case(name)
-    h1, h2, cfg = S.numpy_hops(case)
-    L, qm, n_prb_grid = lp["L"], lp["qm"], case["n_prb_grid"]
-    graph = LD.LdpcGraph(gr.rows, gr.n_cols)
-    rm = RM.PuschRateRecovery(c["bg"], c["A"], c["qm"], c["L"], c["G"], device=dev)
-    enc = EN.PuschTransportEncoder.for_rate_recovery(rm, graph)
-    dec = LD.PuschLdpcDecoder.for_rate_recovery(rm, graph)
-    asm = TB.PuschTransportBlock.for_rate_recovery(rm)
-    eq = EQ.PuschEqualizer(h1, h2, L, n_prb_grid, device=dev)
-    mod = MO.PuschModulator.for_equalizer(eq, qm, scramble=True)
-    dem = DM.PuschDemapper(qm, eq.n_data_re * L, out_dtype=torch.int8, llr_scale=4.0, descramble=True, device=dev)
-    assert mod.n_bits == dem.n_bits == rm.n_bits == enc.n_bits == lp["G"] and mod.g_row_bytes == enc.g_row_bytes
-    tb_bits = np.array(E.inputs(name)[0])
-    sent = T.pack(tb_bits, enc.tb_row_bytes)
-    B = len(sent)
-    g = enc(_t(sent), rv=0)
-    pil = DR.PuschDmrs(h1, h2, L, n_prb_grid, device=dev)(M.LOOP_SLOT, M.LOOP_N_ID, M.LOOP_N_SCID)
-    tx = mod(g, pil[0].contiguous(), case["beta"], rnti=M.LOOP_RNTI, n_id=M.LOOP_SCR_ID)
-    H = torch.as_tensor(M.loop_channel(case, np.random.default_rng(81)), device=dev)           # [R, n_sc, L]
-    rx = torch.einsum("rkl,blks->brks", H, tx).contiguous()
-    ch_est, noise, *_ = ES.estimate(rx, pil[0], case["beta"], h1, h2, cfg)
-    x_hat, nvar = eq(rx, ch_est, noise)
-    wrong = torch.full((B,), M.LOOP_RNTI, dtype=torch.int32, device=dev)
+    ch = loop_chain.build(name, dev)
+    sent = ch.sent
+    assert ch.mod.n_bits == ch.dem.n_bits == ch.rm.n_bits == ch.enc.n_bits == ch.lp["G"] and ch.mod.g_row_bytes == ch.enc.g_row_bytes
+    H = torch.as_tensor(M.loop_channel(ch.case, np.random.default_rng(81)), device=dev)           # [R, n_sc, L]
+    rx = torch.einsum("rkl,blks->brks", H, loop_chain.modulate(ch)).contiguous()
+    wrong = torch.full((ch.B,), M.LOOP_RNTI, dtype=torch.int32, device=dev)
     wrong[0] += 1
-
-    def receive(rnti):
-        soft = rm(dem(x_hat, nvar, rnti=rnti, n_id=M.LOOP_SCR_ID), rv=0)
-        hard, status = dec(soft)
-        out, tb_status, cb_status = asm(hard)
-        torch.cuda.synchronize()
-        return out.cpu().numpy(), tb_status.cpu().numpy()
-
-    out, tb_status = receive(M.LOOP_RNTI)
+    out, tb_status = loop_chain.receive(ch, rx)
     assert np.array_equal(out, sent) and not tb_status.any(), (name, tb_status.tolist())
-    out, tb_status = receive(wrong)
+    out, tb_status = loop_chain.receive(ch, rx, rnti=wrong)
     assert tb_status[0, 0] != 0 and not tb_status[1:].any() and np.array_equal(out[1:], sent[1:]), (name, "wrong rnti", tb_status.tolist())

@@ -15,13 +15,11 @@ import numpy as np
 import pytest
 import torch
 
-import enc_oracle as E
+import loop_chain
 import mod_oracle as MO
-import tb_oracle as TBO
 import tp_oracle as T
 import tpre_oracle as P
-from srsran_ce_pytorch_amd import _lib, demod as DM, deprecode as DP, dmrs as DR, encoder as EN, equalizer as EQ, estimator as ES, ldpc as LD
-from srsran_ce_pytorch_amd import modulator as MD, precode as PR, ratematch as RM, synth as S, transportblock as TB
+from srsran_ce_pytorch_amd import _lib, deprecode as DP, modulator as MD, precode as PR
 
 pytestmark = pytest.mark.gpu
 
@@ -287,44 +285,20 @@ def test_the_dft_s_ofdm_loop_returns_the_transport_block():
     PuschTransformDeprecoder.for_equalizer(eq) -> PuschDemapper(descramble, int8) -> PuschRateRecovery -> PuschLdpcDecoder ->
     PuschTransportBlock on the bg2_z7_rep geometry: the transport block sent comes back with tb_status 0; a slot whose rnti
     differs between modulator and demapper fails its CRC, and so does every slot when the precoder is skipped."""
-    dev, name = _dev(), P.LOOP_NAME
-    c, lp, gr, case = E.CASE_BY_NAME[name], E.LOOPS[name], E.graph(name), MO.loop_case(name)
-    h1, h2, cfg = S.numpy_hops(case)
-    L, qm, n_prb_grid = lp["L"], lp["qm"], case["n_prb_grid"]
-    graph = LD.LdpcGraph(gr.rows, gr.n_cols)
-    rm = RM.PuschRateRecovery(c["bg"], c["A"], c["qm"], c["L"], c["G"], device=dev)
-    enc = EN.PuschTransportEncoder.for_rate_recovery(rm, graph)
-    dec = LD.PuschLdpcDecoder.for_rate_recovery(rm, graph)
-    asm = TB.PuschTransportBlock.for_rate_recovery(rm)
-    eq = EQ.PuschEqualizer(h1, h2, L, n_prb_grid, device=dev)
-    mod = MD.PuschModulator.for_equalizer(eq, qm, scramble=True)
-    pre = PR.PuschTransformPrecoder.for_modulator(mod)
-    tp = DP.PuschTransformDeprecoder.for_equalizer(eq)
-    dem = DM.PuschDemapper(qm, eq.n_data_re * L, out_dtype=torch.int8, llr_scale=4.0, descramble=True, device=dev)
-    assert mod.n_bits == dem.n_bits == rm.n_bits == enc.n_bits == lp["G"] and mod.g_row_bytes == enc.g_row_bytes
-    assert (pre.n_prbs, pre.n_symbols) == (tp.n_prbs, tp.n_symbols) == (4, 5) and pre.n_symbols * pre.m_sc == eq.n_data_re
-    tb_bits = np.array(E.inputs(name)[0])
-    sent = TBO.pack(tb_bits, enc.tb_row_bytes)
-    B = len(sent)
-    g = enc(_t(sent), rv=0)
-    pil = DR.PuschDmrs(h1, h2, L, n_prb_grid, device=dev)(MO.LOOP_SLOT, MO.LOOP_N_ID, MO.LOOP_N_SCID)
-    plain = mod(g, pil[0].contiguous(), case["beta"], rnti=MO.LOOP_RNTI, n_id=MO.LOOP_SCR_ID)
-    tx = pre.grid_(mod(g, pil[0].contiguous(), case["beta"], rnti=MO.LOOP_RNTI, n_id=MO.LOOP_SCR_ID))
+    dev = _dev()
+    ch = loop_chain.build(P.LOOP_NAME, dev)
+    pre, tp, sent = ch.pre, ch.tp, ch.sent
+    assert ch.mod.n_bits == ch.dem.n_bits == ch.rm.n_bits == ch.enc.n_bits == ch.lp["G"] and ch.mod.g_row_bytes == ch.enc.g_row_bytes
+    assert (pre.n_prbs, pre.n_symbols) == (tp.n_prbs, tp.n_symbols) == (4, 5) and pre.n_symbols * pre.m_sc == ch.eq.n_data_re
+    plain = loop_chain.modulate(ch)
+    tx = pre.grid_(loop_chain.modulate(ch))
     assert torch.equal(tx[:, :, :, 2], plain[:, :, :, 2]) and not torch.equal(tx, plain)          # the DM-RS symbol stays, the data rows do not
-    H = torch.as_tensor(MO.loop_channel(case, np.random.default_rng(81)), device=dev)           # [R, n_sc, L]
-    wrong = torch.full((B,), MO.LOOP_RNTI, dtype=torch.int32, device=dev)
+    H = torch.as_tensor(MO.loop_channel(ch.case, np.random.default_rng(81)), device=dev)        # [R, n_sc, L]
+    wrong = torch.full((ch.B,), MO.LOOP_RNTI, dtype=torch.int32, device=dev)
     wrong[0] += 1
 
     def receive(grid, rnti):
-        rx = torch.einsum("rkl,blks->brks", H, grid).contiguous()
-        ch_est, noise, *_ = ES.estimate(rx, pil[0], case["beta"], h1, h2, cfg)
-        x_hat, nvar = eq(rx, ch_est, noise)
-        x, nv = tp(x_hat, nvar)
-        soft = rm(dem(x, nv, rnti=rnti, n_id=MO.LOOP_SCR_ID), rv=0)
-        hard, status = dec(soft)
-        out, tb_status, cb_status = asm(hard)
-        torch.cuda.synchronize()
-        return out.cpu().numpy(), tb_status.cpu().numpy()
+        return loop_chain.receive(ch, torch.einsum("rkl,blks->brks", H, grid).contiguous(), rnti=rnti, deprecode=True)
 
     out, tb_status = receive(tx, MO.LOOP_RNTI)
     assert np.array_equal(out, sent) and not tb_status.any(), tb_status.tolist()

@@ -15,13 +15,11 @@ import numpy as np
 import pytest
 import torch
 
-import enc_oracle as E
+import loop_chain
 import mod_oracle as MO
 import ofdm_oracle as O
-import tb_oracle as TBO
 import tpre_oracle as P
-from srsran_ce_pytorch_amd import _lib, demod as DM, deprecode as DP, dmrs as DR, encoder as EN, equalizer as EQ, estimator as ES, ldpc as LD
-from srsran_ce_pytorch_amd import modulator as MD, ofdm as OF, precode as PR, ratematch as RM, synth as S, transportblock as TB
+from srsran_ce_pytorch_amd import _lib, ofdm as OF
 
 pytestmark = pytest.mark.gpu
 
@@ -282,36 +280,20 @@ def test_the_loop_from_samples_returns_the_transport_block():
     N = 512, 30 kHz, 7680 samples per slot): the transport block sent comes back with tb_status 0 both ways; a slot whose
     samples are rotated by N / 2 fails alone; a demodulator built without the phasors fails every slot (at f0 = 10 kHz the
     DM-RS symbol 2 and the data symbols 0, 1, 3, 4, 5 differ by 103, 128, 128, 103 and 25 degrees)."""
-    dev, name = _dev(), P.LOOP_NAME
-    c, lp, gr, case = E.CASE_BY_NAME[name], E.LOOPS[name], E.graph(name), MO.loop_case(name)
-    h1, h2, cfg = S.numpy_hops(case)
-    L, qm, n_prb_grid = lp["L"], lp["qm"], case["n_prb_grid"]
+    dev = _dev()
+    ch = loop_chain.build(P.LOOP_NAME, dev)
+    case, L, n_prb_grid, mod, sent, B = ch.case, ch.L, ch.n_prb_grid, ch.mod, ch.sent, ch.B
     N, a = LOOP_N, LOOP_ADVANCE
     cp = OF.nr_cp_lengths(LOOP_SCS, N)
     assert case["scs"] == LOOP_SCS and n_prb_grid == 24 and OF.min_fft_size(n_prb_grid) == N and max(LOOP_DELAYS) < min(cp) - a
     phi = OF.nr_symbol_phasors(LOOP_F0, LOOP_SCS, N, cp)
     turn = np.angle(phi / phi[2]) / (2 * np.pi)
     assert all(abs(turn[l]) > 0.06 for l in (0, 1, 3, 4, 5)) and sum(abs(turn[l]) > 0.25 for l in (0, 1, 3, 4, 5)) == 4
-    graph = LD.LdpcGraph(gr.rows, gr.n_cols)
-    rm = RM.PuschRateRecovery(c["bg"], c["A"], c["qm"], c["L"], c["G"], device=dev)
-    enc = EN.PuschTransportEncoder.for_rate_recovery(rm, graph)
-    dec = LD.PuschLdpcDecoder.for_rate_recovery(rm, graph)
-    asm = TB.PuschTransportBlock.for_rate_recovery(rm)
-    eq = EQ.PuschEqualizer(h1, h2, L, n_prb_grid, device=dev)
-    mod = MD.PuschModulator.for_equalizer(eq, qm, scramble=True)
-    pre = PR.PuschTransformPrecoder.for_modulator(mod)
-    tp = DP.PuschTransformDeprecoder.for_equalizer(eq)
-    dem = DM.PuschDemapper(qm, eq.n_data_re * L, out_dtype=torch.int8, llr_scale=4.0, descramble=True, device=dev)
     ofdm = OF.PuschOfdmDemodulator(N, n_prb_grid, cp, window_advance=a, sym_phasor=phi, device=dev)
     bare = OF.PuschOfdmDemodulator(N, n_prb_grid, cp, window_advance=a, device=dev)
     assert ofdm.n_samples == 7680 and (ofdm.n_sc, ofdm.n_sym) == (mod.n_sc, mod.n_sym) and L == 1
-    tb_bits = np.array(E.inputs(name)[0])
-    sent = TBO.pack(tb_bits, enc.tb_row_bytes)
-    B = len(sent)
-    g = enc(_t(sent), rv=0)
-    pil = DR.PuschDmrs(h1, h2, L, n_prb_grid, device=dev)(MO.LOOP_SLOT, MO.LOOP_N_ID, MO.LOOP_N_SCID)
-    plain = mod(g, pil[0].contiguous(), case["beta"], rnti=MO.LOOP_RNTI, n_id=MO.LOOP_SCR_ID)
-    precoded = pre.grid_(mod(g, pil[0].contiguous(), case["beta"], rnti=MO.LOOP_RNTI, n_id=MO.LOOP_SCR_ID))
+    plain = loop_chain.modulate(ch)
+    precoded = ch.pre.grid_(loop_chain.modulate(ch))
     torch.cuda.synchronize()
     rng = np.random.default_rng(82)
     taps = np.zeros((MO.LOOP_PORTS, max(LOOP_DELAYS) + 1), complex)
@@ -324,16 +306,7 @@ def test_the_loop_from_samples_returns_the_transport_block():
         return _t(np.stack([[np.convolve(s[b], taps[r])[:s.shape[1]] for r in range(MO.LOOP_PORTS)] for b in range(B)]).astype(np.complex64))
 
     def receive(samples, demodulator, deprecode):
-        rx = demodulator(samples)
-        ch_est, noise, *_ = ES.estimate(rx, pil[0], case["beta"], h1, h2, cfg)
-        x, nv = eq(rx, ch_est, noise)
-        if deprecode:
-            x, nv = tp(x, nv)
-        soft = rm(dem(x, nv, rnti=MO.LOOP_RNTI, n_id=MO.LOOP_SCR_ID), rv=0)
-        hard, status = dec(soft)
-        out, tb_status, cb_status = asm(hard)
-        torch.cuda.synchronize()
-        return out.cpu().numpy(), tb_status.cpu().numpy()
+        return loop_chain.receive(ch, demodulator(samples), deprecode=deprecode)
 
     for tx, deprecode in ((plain, False), (precoded, True)):
         samples = air(tx)

@@ -147,6 +147,34 @@ def _butterfly_f32(R, xr, xi):
     return [add(add(x[0], t1), t2), add_j(m1, n1), add_j(m2, n2), sub_j(m2, n2), sub_j(m1, n1)]
 
 
+def passes_f32(re, im, radix, tw, scale):
+    """(re, im) float32 [rows, M] through the kernel's passes (csrc/ce_fft.h `tp_passes`) over `radix` with the twiddle table
+    `tw` (complex64 [M]); the last pass multiplies by `scale`, a float32 scalar or one per row ([rows, 1])."""
+    M = re.shape[1]
+    wr, wi = tw.real.astype(F), tw.imag.astype(F)
+    s = 1
+    for n, R in enumerate(radix):
+        last = n == len(radix) - 1
+        nb = M // R
+        i = np.arange(nb)
+        y = _butterfly_f32(R, [re[:, i + k * nb] for k in range(R)], [im[:, i + k * nb] for k in range(R)])
+        ps = (i // s) * s
+        o = (i - ps) + ps * R
+        nre, nim = np.empty_like(re), np.empty_like(im)
+        for j in range(R):
+            yr, yi = y[j]
+            if last:
+                yr, yi = (scale * yr).astype(F), (scale * yi).astype(F)
+            elif j:
+                a, b = wr[ps * j], wi[ps * j]
+                yr, yi = ((yr * a).astype(F) - (yi * b).astype(F)).astype(F), ((yr * b).astype(F) + (yi * a).astype(F)).astype(F)
+            nre[:, o + s * j], nim[:, o + s * j] = yr, yi
+        re, im = nre, nim
+        s *= R
+    assert re.dtype == F and im.dtype == F
+    return re, im
+
+
 def deprecode_f32(x_hat, nvar, view, tw):
     """(x_out complex64, nvar_out float32), both [B, S M].  `view`: the library's host view of the shape; `tw`: its twiddle
     table (complex64 [M])."""
@@ -168,26 +196,7 @@ def deprecode_f32(x_hat, nvar, view, tw):
     with np.errstate(all="ignore"):
         scale = np.where(some, (F(np.sqrt(float(M))) / sb).astype(F), F(0))
         nvo = np.where(some, (sg / sb).astype(F), F(np.inf))
-    wr, wi = tw.real.astype(F), tw.imag.astype(F)
-    s = 1
-    for n, R in enumerate(radix):
-        last = n == len(radix) - 1
-        nb = M // R
-        i = np.arange(nb)
-        y = _butterfly_f32(R, [re[:, i + k * nb] for k in range(R)], [im[:, i + k * nb] for k in range(R)])
-        ps = (i // s) * s
-        o = (i - ps) + ps * R
-        nre, nim = np.empty_like(re), np.empty_like(im)
-        for j in range(R):
-            yr, yi = y[j]
-            if last:
-                yr, yi = (scale[:, None] * yr).astype(F), (scale[:, None] * yi).astype(F)
-            elif j:
-                a, b = wr[ps * j], wi[ps * j]
-                yr, yi = ((yr * a).astype(F) - (yi * b).astype(F)).astype(F), ((yr * b).astype(F) + (yi * a).astype(F)).astype(F)
-            nre[:, o + s * j], nim[:, o + s * j] = yr, yi
-        re, im = nre, nim
-        s *= R
+    re, im = passes_f32(re, im, radix, tw, scale[:, None])
     out = (re + 1j * im).astype(np.complex64)
     assert re.dtype == F and nvo.dtype == F
     return out.reshape(B, -1), np.repeat(nvo, M).reshape(B, -1)

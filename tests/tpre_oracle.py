@@ -2,8 +2,8 @@
 on, and the tolerance rule they follow.
 
 The float64 reference is `tp_oracle.precode` (TS 38.211 6.3.1.4 literally; an explicit M x M matrix up to M = 512).
-`precode_f32` restates the kernel's float32 arithmetic -- conjugate, the pass loop of `tp_oracle.deprecode_f32` with
-`tp_oracle._butterfly_f32` over the radix sequence and the twiddle table of the library's host entry points, the scale
+`precode_f32` restates the kernel's float32 arithmetic -- conjugate, `tp_oracle.passes_f32` (the de-precoder
+restatement's passes) over the radix sequence and the twiddle table of the library's host entry points, the scale
 float32(1 / sqrt(M)) in the last pass, conjugate -- only to calibrate the tolerance.
 
 Tolerance rule, per output i of a row (eps = 2^-24, rms_row = the rms of the row's reference outputs), the shape of
@@ -42,27 +42,7 @@ def precode_f32(x, view, tw) -> np.ndarray:
     x = x.reshape(-1, M)
     re, im = x.real.astype(F), (-x.imag).astype(F)                   # conjugate on load: exact
     scale = F(1.0 / np.sqrt(float(M)))                               # in double, rounded once
-    wr, wi = tw.real.astype(F), tw.imag.astype(F)
-    s = 1
-    for n, R in enumerate(radix):
-        last = n == len(radix) - 1
-        nb = M // R
-        i = np.arange(nb)
-        y = T._butterfly_f32(R, [re[:, i + k * nb] for k in range(R)], [im[:, i + k * nb] for k in range(R)])
-        ps = (i // s) * s
-        o = (i - ps) + ps * R
-        nre, nim = np.empty_like(re), np.empty_like(im)
-        for j in range(R):
-            yr, yi = y[j]
-            if last:
-                yr, yi = (scale * yr).astype(F), (scale * yi).astype(F)
-            elif j:
-                a, b = wr[ps * j], wi[ps * j]
-                yr, yi = ((yr * a).astype(F) - (yi * b).astype(F)).astype(F), ((yr * b).astype(F) + (yi * a).astype(F)).astype(F)
-            nre[:, o + s * j], nim[:, o + s * j] = yr, yi
-        re, im = nre, nim
-        s *= R
-    assert re.dtype == F and im.dtype == F
+    re, im = T.passes_f32(re, im, radix, tw, scale)
     out = np.empty(re.shape, np.complex64)
     out.real, out.imag = re, -im                                     # conjugate on store: exact
     return out.reshape(B, -1)
