@@ -2,8 +2,9 @@
  * ce_tp.h -- EXTENSION of libce_hip.so with NO counterpart in the reference: transform de-precoding (DFT-s-OFDM, the
  * inverse of TS 38.211 6.3.1.4) between ce_eq_equalize and ce_demod_demap, with the per-RE noise variances combined
  * into the per-symbol one the demapper needs.  Behind it, further down: transform precoding, the forward direction
- * (ce_tp_precode), and OFDM demodulation, samples to the resource grid (ce_ofdm_*), which runs the same passes over the
- * same host view at the lengths 128 .. 4096.
+ * (ce_tp_precode), OFDM demodulation, samples to the resource grid (ce_ofdm_*), which runs the same passes over the
+ * same host view at the lengths 128 .. 4096, and OFDM modulation, the grid to samples, on the demodulator's plan
+ * (ce_ofdmtx_modulate).
  *
  * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
  * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
@@ -201,6 +202,44 @@ void ce_ofdm_plan_destroy(ce_ofdm_plan* plan);
 
 int ce_ofdm_demodulate(const ce_ofdm_plan* plan, const void* samples, int64_t slot_stride, int64_t port_stride, int64_t n_slots,
                        int64_t n_ports, void* out, void* stream);
+
+/*
+ * OFDM MODULATION, the transmit side behind ce_mod_modulate (and ce_tp_precode): the resource grid to the time-domain
+ * samples of a slot, on a ce_ofdm_plan -- the mapping of the grid's subcarriers onto the bins around DC, a transform of
+ * length N per symbol with the same Stockham passes, radix sequence, twiddle table and launch geometry as the
+ * demodulator, and the cyclic prefix in front of every symbol.  The plan's window_advance is a receiver value and is
+ * ignored.  For slot b, port r, symbol l and n = -cp_len[l] .. N - 1, with s = samples + b slot_stride + r port_stride:
+ *     s[t_l + cp_len[l] + n] = N^(-1/2) sum_{k<n_sc} conj(phi_l) X[b][r][l][k] exp(+j 2 pi q_k n / N)
+ * the operator of tests/ofdm_oracle.py `modulate`.  The scale is unitary; phi_l is the plan's sym_phasor, the
+ * DEMODULATOR's value, of which the modulator applies the conjugate, and only where phasors were given.  So
+ * ce_ofdm_demodulate with the same plan values returns X through an ideal channel, for any advance a <= min cp_len.
+ * One grid row per port: there is no layer-to-port precoding matrix, no windowing or overlap-add between symbols.
+ *
+ * float32 arithmetic (restated in tests/ofdm_tx_oracle.py `modulate_f32`): where phasors were given, X is multiplied by
+ * (phi_l.re, -phi_l.im) -- the sign flip is exact -- as the complex product (x.re w.re - x.im w.im, x.re w.im + x.im w.re);
+ * the value goes to bin q_k mod N and the other N - n_sc bins are zero; the passes are the inverse transform natively, so
+ * there is no conjugation; the last pass scales by float32(1 / sqrt(N)); the cyclic prefix is the symbol's last
+ * cp_len[l] values stored a second time, bit for bit.  No reduction and no special-value handling: a NaN or an infinity
+ * in a symbol of the grid stays in the cp_len[l] + N samples of that symbol.
+ *
+ *  grid      complex64 [slot][port][n_sym][n_sc], dense, 16-byte aligned, read with 16-byte loads (what ce_mod_modulate
+ *            writes and ce_ofdm_demodulate returns).
+ *  samples   complex64, row (b, r) at b slot_stride + r port_stride, strides in complex elements (a view into a longer
+ *            stream); 8-byte aligned, written with 8-byte stores: cyclic prefixes such as 9 or 10 samples put symbols at
+ *            odd offsets.  Every sample of [0, T) of every row is written exactly once, nothing else.
+ * One launch on `stream`, asynchronous; n_slots == 0 or n_ports == 0 launches nothing, whatever the pointers.  One
+ * 256-thread workgroup handles rows_per_workgroup symbols of one (slot, port).  No atomics, no scratch; every address
+ * comes from the block index, the thread index and host-derived values.
+ * CE_ERR_INVALID: a null plan (refused first) or pointer; a negative count or stride; grid not 16-byte or samples not
+ * 8-byte aligned; strides whose extent exceeds the address space; rows of samples that are not pairwise disjoint --
+ * accepted are the ports inside a slot (port_stride >= T where n_ports > 1, slot_stride >= (n_ports - 1) port_stride + T
+ * where n_slots > 1) and the slots inside a port, one continuous stream per port (slot_stride >= T where n_slots > 1,
+ * port_stride >= (n_slots - 1) slot_stride + T where n_ports > 1); the extent
+ * (n_slots - 1) slot_stride + (n_ports - 1) port_stride + T of samples overlapping grid.
+ * CE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups in one launch.
+ */
+int ce_ofdmtx_modulate(const ce_ofdm_plan* plan, const void* grid, int64_t n_slots, int64_t n_ports, void* samples,
+                       int64_t slot_stride, int64_t port_stride, void* stream);
 
 #ifdef __cplusplus
 }

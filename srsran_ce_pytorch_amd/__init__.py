@@ -4,7 +4,7 @@ from .deprecode import PuschTransformDeprecoder  # noqa: F401
 from .encoder import PuschTransportEncoder  # noqa: F401
 from .ldpc import LdpcGraph, PuschLdpcDecoder  # noqa: F401
 from .modulator import PuschModulator  # noqa: F401
-from .ofdm import PuschOfdmDemodulator  # noqa: F401
+from .ofdm import PuschOfdmDemodulator, PuschOfdmModulator  # noqa: F401
 from .precode import PuschTransformPrecoder  # noqa: F401
 from .ratematch import PuschRateRecovery, select_base_graph  # noqa: F401
 from .transportblock import PuschTransportBlock  # noqa: F401

@@ -260,6 +260,8 @@ REGISTRY["ce_tp.h"] = Header(structs={"ce_tp_desc": TpDesc, "ce_tp_info": TpInfo
     "ce_ofdm_plan_create": (_int, [_i32, _i32, _i32, _i32, _i32, _P(_i32), _i32, _fp, _P(_vp)]),
     "ce_ofdm_plan_destroy": (None, [_vp]),
     "ce_ofdm_demodulate": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    # OFDM modulation on the demodulator's plan (the name keeps clear of the ce_ofdm_ prefix)
+    "ce_ofdmtx_modulate": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
 })
 CE_LDPC_MAX_ZC, CE_LDPC_MAX_ROWS, CE_LDPC_MAX_COLS, CE_LDPC_MAX_ROW_DEGREE = 384, 46, 68, 19
 CE_LDPC_L_BOUND, CE_LDPC_LDS_MAX, CE_LDPC_F32, CE_LDPC_I8 = 4497, 163840, 0, 1

@@ -1,7 +1,8 @@
-// What the row transforms (ce_tp.hip: transform de-precoding and precoding; ce_ofdm.hip: OFDM demodulation) share: on the
-// device the row frame of a workgroup and the Stockham passes of one row in LDS, on the host the radix sequence, stride
-// constants, launch geometry and twiddle table of a transform of any length 2^a 3^b 5^c and the part of a plan that holds
-// them.  The loads and stores differ per kernel and stay there.  Internal; everything here has internal linkage.
+// What the row transforms (ce_tp.hip: transform de-precoding and precoding; ce_ofdm.hip: OFDM demodulation and modulation)
+// share: on the device the row frame of a workgroup and the Stockham passes of one row in LDS, on the host the radix
+// sequence, stride constants, launch geometry and twiddle table of a transform of any length 2^a 3^b 5^c and the part of a
+// plan that holds them.  The loads and stores differ per kernel and stay there.  Internal; everything here has internal
+// linkage.
 //
 //   frame  one 256-thread workgroup handles rows_per_workgroup rows of one item (a slot, or a (slot, port)),
 //          threads_per_row = 64, 128 or 256 threads each: whole waves, so everything that depends on the row is

@@ -1,6 +1,7 @@
 // EXTENSION (no reference counterpart, see include/ce_tp.h): OFDM demodulation -- per (slot, port, symbol) the window of N
 // time-domain samples behind the cyclic prefix, its DFT of length N = 2^n scaled by 1 / sqrt(N), and the n_sc bins around
 // DC onto the subcarriers of the resource grid, with the window advance and the per-symbol phase compensated at the store.
+// Behind it, on the same plan, the transmit direction: OFDM modulation (ce_ofdmtx_kernel).
 //
 // Kernel: the row frame of ce_fft.h, a row being a window (symbol) of one (slot, port): 64 KiB of LDS at N = 4096, two
 // workgroups per CU.
@@ -81,6 +82,65 @@ __global__ __launch_bounds__(TP_NT) void ce_ofdm_kernel(OfdmDev P, const float2*
   }
 }
 
+// OFDM MODULATION, the transmit direction on the same plan: per (slot, port, symbol) the n_sc subcarriers of the grid onto
+// the bins around DC, the transform of length N -- the passes are the inverse transform natively, so there is no
+// conjugation -- scaled by 1 / sqrt(N), and the cp_l + N samples of the symbol with its cyclic prefix in front.
+//   load   thread t of the row takes the pairs of subcarriers k = 2 h, 2 h + 1, h = t, t + threads_per_row, ..: one 16-byte
+//          global load, contiguous over the lanes, the product with conj(phi_l) where phasors were given, one 16-byte LDS
+//          write at bin (k - n_sc / 2) mod N; the N - n_sc bins n_sc / 2 .. N - n_sc / 2 - 1 in between are written with
+//          zeros, 16 bytes at a time (n_sc / 2 and N - n_sc are even).  An inactive row writes zeros and loads nothing.
+//   passes as above, without the conjugations.
+//   store  thread t takes the samples j = t, t + threads_per_row, .. < cp_l + N of the symbol: sample j is the result's
+//          element (j - cp_l) mod N, so the prefix is the symbol's tail stored a second time; 8-byte stores (a symbol may
+//          start at an odd sample), contiguous over the lanes.  Every sample of [0, T) of a (slot, port) exactly once.
+struct OfdmTxDev {
+  FftDev f;               // the demodulator's
+  uint32_t n_sc;
+  uint32_t has_phasor;
+  float scale;            // float32(1 / sqrt(N))
+  int32_t start[CE_MAX_SYMBOLS];    // t_l, samples from the start of the slot; entries >= n_sym are 0
+  int32_t cp[CE_MAX_SYMBOLS];       // cp_l
+  float2 phasor[CE_MAX_SYMBOLS];    // phi_l, the demodulator's: applied conjugated
+};
+
+__global__ __launch_bounds__(TP_NT) void ce_ofdmtx_kernel(OfdmTxDev P, const float2* __restrict__ tw, const float4* __restrict__ grid, uint32_t n_ports,
+                                                          float2* __restrict__ samples, int64_t slot_stride, int64_t port_stride) {
+  extern __shared__ float4 ofdm_lds[];
+  const auto [item, row, lane, tpr, active, buf0, buf1] = fft_row(P.f, ofdm_lds);   // item = slot n_ports + port
+  const uint32_t N = P.f.m, mask = N - 1u, n_half = P.n_sc >> 1;
+  const uint32_t slot = item / n_ports, port = item - slot * n_ports;
+  const uint32_t ri = active ? row : 0u;
+
+  // ---- load: conj(phi) X onto the bins around DC, zeros in between (an inactive row: zeros) ----
+  {
+    const float2 phi = make_float2(P.phasor[ri].x, -P.phasor[ri].y);
+    const float4* x = grid + ((((int64_t)item * P.f.n_rows + ri) * (int64_t)P.n_sc) >> 1);
+    for (uint32_t h = lane; h < n_half; h += tpr) {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (active) v = x[h];
+      float2 y0 = make_float2(v.x, v.y), y1 = make_float2(v.z, v.w);
+      if (P.has_phasor) {
+        y0 = tp_cmul(y0, phi);
+        y1 = tp_cmul(y1, phi);
+      }
+      const uint32_t q = 2u * h - n_half;   // q_k of k = 2 h in two's complement: N divides 2^32, so `& mask` is mod N
+      *reinterpret_cast<float4*>(buf0 + (q & mask)) = make_float4(y0.x, y0.y, y1.x, y1.y);
+    }
+    const uint32_t n_guard = (N - P.n_sc) >> 1;   // pairs of unused bins
+    for (uint32_t g = lane; g < n_guard; g += tpr) *reinterpret_cast<float4*>(buf0 + (n_half + 2u * g)) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  __syncthreads();
+
+  const float2* res = tp_passes(P.f, buf0, buf1, tw, lane, tpr, P.scale);
+
+  // ---- store: the cyclic prefix and the symbol ----
+  if (active) {
+    const uint32_t cp = (uint32_t)P.cp[ri], len = cp + N;
+    float2* s = samples + ((int64_t)slot * slot_stride + (int64_t)port * port_stride + (int64_t)P.start[ri]);
+    for (uint32_t j = lane; j < len; j += tpr) s[j] = res[(j - cp) & mask];
+  }
+}
+
 // ---- host derivation ----
 
 // Validation of the plan values (all but the phasors); the view, the window starts w_l into `win` (CE_MAX_SYMBOLS
@@ -111,11 +171,27 @@ int ofdm_derive(int32_t n_fft, int32_t n_prb_grid, int32_t n_sym, const int32_t*
   return CE_OK;
 }
 
+// What both launches check about a non-empty batch behind their pointers: the workgroup count, into *n_wg, and that the
+// extent of the strided tensor, in bytes, stays inside 64 bits.
+int ofdm_batch(const FftDev& f, int64_t n_slots, int64_t n_ports, int64_t slot_stride, int64_t port_stride, int64_t* n_wg) {
+  const int64_t lim = 0x7FFFFFFFll;
+  if (n_slots > lim || n_ports > lim || n_slots * n_ports > lim / (int64_t)f.wg_per_item)
+    return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots x %lld ports of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots,
+                   (long long)n_ports, f.wg_per_item);
+  *n_wg = n_slots * n_ports * (int64_t)f.wg_per_item;
+  const int64_t room = INT64_MAX >> 6;   // n_slots, n_ports < 2^31 here
+  if (slot_stride > room / n_slots || port_stride > room / n_ports)
+    return ce_fail(CE_ERR_INVALID, "slot_stride=%lld and port_stride=%lld: the extent of %lld slots x %lld ports exceeds the address space",
+                   (long long)slot_stride, (long long)port_stride, (long long)n_slots, (long long)n_ports);
+  return CE_OK;
+}
+
 }  // namespace
 
 struct ce_ofdm_plan {
   FftPlan core;
   OfdmDev dev{};
+  OfdmTxDev tx{};          // the modulator's argument block of the same values
   int32_t n_samples = 0;   // T
 };
 
@@ -155,6 +231,16 @@ extern "C" int ce_ofdm_plan_create(int32_t abi_version, int32_t device, int32_t 
   D.adv = (uint32_t)window_advance;
   D.has_phasor = sym_phasor ? 1u : 0u;
   D.scale = (float)(1.0 / sqrt((double)n_fft));
+  OfdmTxDev& X = p->tx;
+  X.f = D.f;
+  X.n_sc = D.n_sc;
+  X.has_phasor = D.has_phasor;
+  X.scale = D.scale;
+  for (int l = 0, t = 0; l < n_sym; t += cp_len[l] + n_fft, ++l) {
+    X.start[l] = t;
+    X.cp[l] = cp_len[l];
+    X.phasor[l] = D.phasor[l];
+  }
   const hipError_t e = fft_plan_upload(&p->core, device, v);
   if (e != hipSuccess) {
     ce_ofdm_plan_destroy(p.release());
@@ -177,16 +263,8 @@ extern "C" int ce_ofdm_demodulate(const ce_ofdm_plan* p, const void* samples, in
   if (reinterpret_cast<uintptr_t>(samples) & 7u) return ce_fail(CE_ERR_INVALID, "samples must be 8-byte aligned");
   if (reinterpret_cast<uintptr_t>(out) & 15u) return ce_fail(CE_ERR_INVALID, "out must be 16-byte aligned");
   const OfdmDev& D = p->dev;
-  const int64_t lim = 0x7FFFFFFFll;
-  if (n_slots > lim || n_ports > lim || n_slots * n_ports > lim / (int64_t)D.f.wg_per_item)
-    return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots x %lld ports of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots,
-                   (long long)n_ports, D.f.wg_per_item);
-  const int64_t n_wg = n_slots * n_ports * (int64_t)D.f.wg_per_item;
-  // n_slots, n_ports < 2^31 here; the extents below, in bytes, must stay inside 64 bits
-  const int64_t room = INT64_MAX >> 6;
-  if (slot_stride > room / n_slots || port_stride > room / n_ports)
-    return ce_fail(CE_ERR_INVALID, "slot_stride=%lld and port_stride=%lld: the extent of %lld slots x %lld ports exceeds the address space",
-                   (long long)slot_stride, (long long)port_stride, (long long)n_slots, (long long)n_ports);
+  int64_t n_wg;
+  if (const int rc = ofdm_batch(D.f, n_slots, n_ports, slot_stride, port_stride, &n_wg); rc != CE_OK) return rc;
   const uintptr_t s0 = reinterpret_cast<uintptr_t>(samples), o0 = reinterpret_cast<uintptr_t>(out);
   const uintptr_t s1 = s0 + 8u * (uintptr_t)((n_slots - 1) * slot_stride + (n_ports - 1) * port_stride + p->n_samples);
   const uintptr_t o1 = o0 + 8u * (uintptr_t)(n_slots * n_ports) * D.f.n_rows * D.n_sc;
@@ -196,4 +274,36 @@ extern "C" int ce_ofdm_demodulate(const ce_ofdm_plan* p, const void* samples, in
   hipLaunchKernelGGL(ce_ofdm_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->core.lds_bytes, (hipStream_t)stream, D, p->core.tw,
                      reinterpret_cast<const float2*>(samples), slot_stride, port_stride, (uint32_t)n_ports, reinterpret_cast<float4*>(out));
   return ce_launch_status("OFDM demodulation");
+}
+
+extern "C" int ce_ofdmtx_modulate(const ce_ofdm_plan* p, const void* grid, int64_t n_slots, int64_t n_ports, void* samples, int64_t slot_stride,
+                                  int64_t port_stride, void* stream) {
+  if (!p) return ce_fail(CE_ERR_INVALID, "null argument");
+  if (n_slots < 0 || n_ports < 0) return ce_fail(CE_ERR_INVALID, "n_slots=%lld, n_ports=%lld", (long long)n_slots, (long long)n_ports);
+  if (n_slots == 0 || n_ports == 0) return CE_OK;
+  if (!grid || !samples) return ce_fail(CE_ERR_INVALID, "null argument");
+  if (slot_stride < 0 || port_stride < 0)
+    return ce_fail(CE_ERR_INVALID, "slot_stride=%lld and port_stride=%lld must be >= 0", (long long)slot_stride, (long long)port_stride);
+  if (reinterpret_cast<uintptr_t>(grid) & 15u) return ce_fail(CE_ERR_INVALID, "grid must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(samples) & 7u) return ce_fail(CE_ERR_INVALID, "samples must be 8-byte aligned");
+  const OfdmTxDev& D = p->tx;
+  int64_t n_wg;
+  if (const int rc = ofdm_batch(D.f, n_slots, n_ports, slot_stride, port_stride, &n_wg); rc != CE_OK) return rc;
+  // every sample is written by one workgroup only: the rows of T samples pairwise disjoint, the ports inside a slot or the
+  // slots inside a port (one continuous stream per port)
+  const int64_t T = p->n_samples;
+  const bool port_inner = (n_ports == 1 || port_stride >= T) && (n_slots == 1 || slot_stride >= (n_ports - 1) * port_stride + T);
+  const bool slot_inner = (n_slots == 1 || slot_stride >= T) && (n_ports == 1 || port_stride >= (n_slots - 1) * slot_stride + T);
+  if (!port_inner && !slot_inner)
+    return ce_fail(CE_ERR_INVALID, "slot_stride=%lld and port_stride=%lld: the rows of %lld samples of %lld slots x %lld ports overlap",
+                   (long long)slot_stride, (long long)port_stride, (long long)T, (long long)n_slots, (long long)n_ports);
+  const uintptr_t g0 = reinterpret_cast<uintptr_t>(grid), s0 = reinterpret_cast<uintptr_t>(samples);
+  const uintptr_t g1 = g0 + 8u * (uintptr_t)(n_slots * n_ports) * D.f.n_rows * D.n_sc;
+  const uintptr_t s1 = s0 + 8u * (uintptr_t)((n_slots - 1) * slot_stride + (n_ports - 1) * port_stride + T);
+  if (g0 < s1 && s0 < g1) return ce_fail(CE_ERR_INVALID, "samples overlaps grid");
+  CeDeviceScope scope(p->core.device);
+  if (scope.err != hipSuccess) return ce_device_fail(p->core.device, scope.err);
+  hipLaunchKernelGGL(ce_ofdmtx_kernel, dim3((unsigned)n_wg), dim3(TP_NT), (size_t)p->core.lds_bytes, (hipStream_t)stream, D, p->core.tw,
+                     reinterpret_cast<const float4*>(grid), (uint32_t)n_ports, reinterpret_cast<float2*>(samples), slot_stride, port_stride);
+  return ce_launch_status("OFDM modulation");
 }

@@ -1,7 +1,7 @@
-"""OFDM demodulation EXTENSION (include/ce_tp.h `ce_ofdm_demodulate`; the reference stops at the channel estimate): the
-step in front of the estimator -- time-domain I/Q samples of a slot to the resource grid: cyclic-prefix removal, a DFT of
-length N = 2^n per symbol, the bins around DC onto the grid's subcarriers, the window advance and the per-symbol phase of
-TS 38.211 5.4 compensated; one launch on the current stream.
+"""OFDM demodulation and modulation EXTENSION (include/ce_tp.h `ce_ofdm_demodulate`, `ce_ofdmtx_modulate`; the reference
+stops at the channel estimate).  ``PuschOfdmDemodulator`` is the step in front of the estimator -- time-domain I/Q samples of
+a slot to the resource grid: cyclic-prefix removal, a DFT of length N = 2^n per symbol, the bins around DC onto the grid's
+subcarriers, the window advance and the per-symbol phase of TS 38.211 5.4 compensated; one launch on the current stream.
 
     cp = nr_cp_lengths(30e3, 4096)                                            # 352, 288 x 13
     dem = PuschOfdmDemodulator(4096, 273, cp, window_advance=cp[1] // 2,
@@ -9,7 +9,14 @@ TS 38.211 5.4 compensated; one launch on the current stream.
     received_rg = dem(samples)                                                # [B, R, >= 61440] -> [B, R, 3276, 14]
     ch_est, noise, *_ = estimate(received_rg, pilots, beta, hop1, hop2, cfg)
 
-Out of scope: the transmit direction (IFFT and CP insertion), int16 or fp16 samples, a k0 or 7.5 kHz shift, PRACH."""
+``PuschOfdmModulator`` is the transmit direction behind ``PuschModulator`` (and ``PuschTransformPrecoder``), on the same plan:
+the grid's subcarriers onto the bins around DC, the transform, the cyclic prefix in front of every symbol; one launch.
+
+    tx = PuschModulator(...)(g, pilots, beta_dmrs, rnti=rnti, n_id=n_id)      # [B, R, 3276, 14], one grid row per port
+    samples = PuschOfdmModulator.for_demodulator(dem)(tx)                     # [B, R, 61440]
+
+Out of scope: a layer-to-port precoding matrix (identity: one grid row per port), windowing or overlap-add between symbols,
+int16 or fp16 samples, a k0 or 7.5 kHz shift, PRACH."""
 from __future__ import annotations
 
 import ctypes as C
@@ -91,12 +98,24 @@ def twiddles(n_fft: int) -> np.ndarray:
     return w
 
 
-class PuschOfdmDemodulator(_stage.Stage):
-    _CREATE, _DESTROY, _LAUNCH = "ce_ofdm_plan_create", "ce_ofdm_plan_destroy", "ce_ofdm_demodulate"
-    _NOUN = "the OFDM demodulator"
+def _row_strides(name: str, t: torch.Tensor, T: int):
+    """(slot stride, port stride) in elements of the complex64 rows ``t[B, R, >= T]``, 0 where the dimension has one entry,
+    or ``ValueError`` where the last row's T samples lie behind what the tensor's storage holds."""
+    B, R = int(t.shape[0]), int(t.shape[1])
+    ss, ps = (int(t.stride(0)) if B > 1 else 0), (int(t.stride(1)) if R > 1 else 0)
+    if ss < 0 or ps < 0:
+        raise ValueError("negative strides are not supported")
+    held = t.untyped_storage().nbytes() // 8 - int(t.storage_offset())
+    if (B - 1) * ss + (R - 1) * ps + T > held:
+        raise ValueError(f"{name}: strides ({ss}, {ps}) put the last row's {T} samples behind the {held} the tensor holds")
+    return ss, ps
 
-    def __init__(self, n_fft: int, n_prb_grid: int, cp_len: Sequence[int], n_sym: int = 14, window_advance: int = 0,
-                 sym_phasor=None, device=None):
+
+class _OfdmStage(_stage.Stage):
+    """What the demodulator and the modulator share: the validated plan values and the ``ce_ofdm_plan`` made of them."""
+    _CREATE, _DESTROY = "ce_ofdm_plan_create", "ce_ofdm_plan_destroy"
+
+    def __init__(self, n_fft: int, n_prb_grid: int, cp_len: Sequence[int], n_sym: int, window_advance: int, sym_phasor, device):
         super().__init__(device)
         self.n_fft, self.n_prb_grid, self.n_sym, self.window_advance = int(n_fft), int(n_prb_grid), int(n_sym), int(window_advance)
         view = derive_host(self.n_fft, self.n_prb_grid, cp_len, self.n_sym, self.window_advance)
@@ -117,6 +136,15 @@ class PuschOfdmDemodulator(_stage.Stage):
         phi = None if self.sym_phasor is None else self.sym_phasor.ctypes.data_as(C.POINTER(C.c_float))
         return self._lib.ce_ofdm_plan_create(_lib.CE_ABI_VERSION, int(device_index), self.n_fft, self.n_prb_grid, self.n_sym,
                                              _cp_array(self.cp_len, self.n_sym), self.window_advance, phi, C.byref(handle))
+
+
+class PuschOfdmDemodulator(_OfdmStage):
+    _LAUNCH = "ce_ofdm_demodulate"
+    _NOUN = "the OFDM demodulator"
+
+    def __init__(self, n_fft: int, n_prb_grid: int, cp_len: Sequence[int], n_sym: int = 14, window_advance: int = 0,
+                 sym_phasor=None, device=None):
+        super().__init__(n_fft, n_prb_grid, cp_len, n_sym, window_advance, sym_phasor, device)
 
     def __call__(self, samples: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``received_rg[B, R, n_sc, n_sym]`` complex64 on the current stream: the permuted view of the dense
@@ -139,12 +167,57 @@ class PuschOfdmDemodulator(_stage.Stage):
             _stage.check_dense("out", out, torch.complex64, shape, dev, "complex64")
         if B == 0 or R == 0:
             return out.permute(0, 1, 3, 2)                       # empty batch: nothing to launch
-        ss, ps = (int(samples.stride(0)) if B > 1 else 0), (int(samples.stride(1)) if R > 1 else 0)
-        if ss < 0 or ps < 0:
-            raise ValueError("negative strides are not supported")
-        held = samples.untyped_storage().nbytes() // 8 - int(samples.storage_offset())
-        if (B - 1) * ss + (R - 1) * ps + T > held:
-            raise ValueError(f"samples: strides ({ss}, {ps}) put the last row's {T} samples behind the {held} the tensor holds")
+        ss, ps = _row_strides("samples", samples, T)
         _stage.check_aligned(("out", out))
         self._launch(C.c_void_p(samples.data_ptr()), ss, ps, B, R, C.c_void_p(out.data_ptr()))
         return out.permute(0, 1, 3, 2)
+
+
+class PuschOfdmModulator(_OfdmStage):
+    """The transmit direction (include/ce_tp.h `ce_ofdmtx_modulate`): the resource grid to the samples of a slot -- the
+    subcarriers onto the bins around DC, a transform of length N per symbol scaled by 1 / sqrt(N), the cyclic prefix in front.
+    ``sym_phasor`` is the DEMODULATOR's (``nr_symbol_phasors``): the modulator applies its conjugate, so a demodulator of the
+    same values returns the grid through an ideal channel, whatever its window advance."""
+    _LAUNCH = "ce_ofdmtx_modulate"
+    _NOUN = "the OFDM modulator"
+
+    def __init__(self, n_fft: int, n_prb_grid: int, cp_len: Sequence[int], n_sym: int = 14, sym_phasor=None, device=None):
+        super().__init__(n_fft, n_prb_grid, cp_len, n_sym, 0, sym_phasor, device)
+
+    @classmethod
+    def for_demodulator(cls, dem: PuschOfdmDemodulator, device=None) -> "PuschOfdmModulator":
+        """The modulator whose samples `dem` turns back into the grid: its transform length, grid width, cyclic prefixes,
+        symbol count and phasors (the window advance is the receiver's alone)."""
+        if not isinstance(dem, PuschOfdmDemodulator):
+            raise ValueError(f"dem must be a PuschOfdmDemodulator, got {type(dem).__name__}")
+        return cls(dem.n_fft, dem.n_prb_grid, dem.cp_len, n_sym=dem.n_sym, sym_phasor=dem.sym_phasor,
+                   device=device if device is not None else dem._device_arg)
+
+    def __call__(self, grid: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``samples[B, R, n_samples]`` complex64 on the current stream.  ``grid`` is what ``PuschModulator`` and
+        ``PuschTransformPrecoder.grid_`` return: the permuted complex64 ``[B, R, n_sc, n_sym]`` view of a dense
+        ``[B, R, n_sym, n_sc]`` buffer, one row per port.  ``out`` is a complex64 ``[B, R, >= n_samples]`` tensor with a
+        contiguous last dimension; its slot and port strides are free (a view into a longer stream, the ports inside a slot
+        or the slots of a port one behind the other) as long as no two rows share a sample.  Only the first ``n_samples``
+        samples of each row are written, each exactly once, and they are what is returned; ``out`` may not overlap ``grid``."""
+        self._plan()
+        dev, T = self.device, self.n_samples
+        if not isinstance(grid, torch.Tensor) or grid.device != dev:
+            raise ValueError(f"grid must be a tensor on {dev}")
+        if (grid.dtype != torch.complex64 or grid.dim() != 4 or tuple(grid.shape[2:]) != (self.n_sc, self.n_sym)
+                or not grid.permute(0, 1, 3, 2).is_contiguous()):
+            raise ValueError(f"grid must be a {torch.complex64} tensor [slots, ports, {self.n_sc}, {self.n_sym}] (the permuted view of a dense "
+                             f"[slots, ports, {self.n_sym}, {self.n_sc}] buffer), got {grid.dtype} {tuple(grid.shape)} with strides {tuple(grid.stride())}")
+        B, R = int(grid.shape[0]), int(grid.shape[1])
+        if out is None:
+            out = torch.empty((B, R, T), dtype=torch.complex64, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.complex64 or out.dim() != 3
+              or tuple(out.shape[:2]) != (B, R) or out.shape[2] < T or (out.shape[2] > 1 and out.stride(2) != 1)):
+            got = f"{out.dtype} {tuple(out.shape)} with strides {tuple(out.stride())} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__
+            raise ValueError(f"out must be a {torch.complex64} tensor [{B}, {R}, >= {T}] with a contiguous last dimension on {dev}, got {got}")
+        if B == 0 or R == 0:
+            return out[:, :, :T]                                 # empty batch: nothing to launch
+        ss, ps = _row_strides("out", out, T)
+        _stage.check_aligned(("grid", grid))
+        self._launch(C.c_void_p(grid.data_ptr()), B, R, C.c_void_p(out.data_ptr()), ss, ps)
+        return out[:, :, :T]
