@@ -27,7 +27,8 @@
 //  Codeword.  The columns are packed at Zc-bit granularity into one flat string, which is stored byte-swapped to `cw`
 //   where that is given.
 //  Gather.  One thread builds a whole dword of g: per bit the closed form of ce_rm.h (interleaver row and column, k mod P
-//   where bits repeat, rank + s, unrank round the fillers) and one LDS read.  Where two blocks meet inside a dword of g no
+//   where bits repeat, rank + s, unrank round the fillers) over the words of ce_ratematch.h, which rate recovery walks
+//   too, and one LDS read.  Where two blocks meet inside a dword of g no
 //   workgroup holds all its bits: the gather is then a second launch over g's dwords that reads the codewords from `cw`
 //   (ce_enc.h).
 // DESIGN 6l.
@@ -39,7 +40,7 @@
 
 #include "ce_crc.h"
 #include "ce_enc.h"
-#include "ce_segment.h"
+#include "ce_ratematch.h"
 #include "ce_stage.h"
 
 namespace {
@@ -63,11 +64,9 @@ struct EncDev {
   uint32_t tb_row_dwords, g_row_dwords, cw_row_dwords;
   uint32_t zc, n_sys, n_rows, w, we, kd;   // kd: dwords of the K information bits and one to spare, a multiple of 4
   uint32_t graph_dw;                    // dwords of the plan's table the kernel copies to LDS
-  uint32_t qm, g, f0, nf, prm;          // Qm, G, fillers [f0, f0 + nf), non-filler positions of one turn
-  uint32_t s0, s1, s2, s3;              // per rv: the rank the walk starts at
-  uint32_t n_lo, e_lo, e_hi, eq_lo, eq_hi, base_hi;
-  uint32_t rep;                         // some E_r > prm: bits repeat
-  float inv_prm;
+  RmWalkDev rm;                         // bit selection and interleaving (ce_ratematch.h); rm.p is P, not the payload above
+  uint32_t rep;                         // some E_r > P: bits repeat
+  float inv_prm;                        // float32(1 / P)
   uint32_t two_zc;
 };
 
@@ -118,46 +117,40 @@ __device__ __forceinline__ uint32_t enc_crc(const uint32_t (*T)[256], uint32_t g
   return ce_crc_mulmod(red[0] ^ red[1] ^ red[2] ^ red[3], finv, g, L);
 }
 
-// the rank the walk of redundancy version rv & 3 starts at
-__device__ __forceinline__ uint32_t enc_start(const EncDev& P, uint32_t rv) {
-  const uint32_t b = rv & 3u;
-  return b == 0u ? P.s0 : b == 1u ? P.s1 : b == 2u ? P.s2 : P.s3;
-}
-
 // One dword of g: bits 32 d .. 32 d + 31 of the slot's row, zeros from G on.  word(r, i) is dword i of block r's codeword.
 template <class Word>
 __device__ __forceinline__ uint32_t enc_gather_dword(const EncDev& P, uint32_t d, uint32_t s, Word word) {
   const uint32_t f = d << 5;
-  if (f >= P.g) return 0u;
+  if (f >= P.rm.g) return 0u;
   uint32_t r, fl;   // the first bit's block and its index in the block's E_r bits
-  if (f < P.base_hi) {
-    r = f / P.e_lo;
-    fl = f - r * P.e_lo;
+  if (f < P.rm.base_hi) {
+    r = f / P.rm.e_lo;
+    fl = f - r * P.rm.e_lo;
   } else {
-    r = (f - P.base_hi) / P.e_hi;
-    fl = f - P.base_hi - r * P.e_hi;
-    r += P.n_lo;
+    r = (f - P.rm.base_hi) / P.rm.e_hi;
+    fl = f - P.rm.base_hi - r * P.rm.e_hi;
+    r += P.rm.n_lo;
   }
-  uint32_t e_r = r < P.n_lo ? P.e_lo : P.e_hi, eq = r < P.n_lo ? P.eq_lo : P.eq_hi;
-  uint32_t j = fl / P.qm, i = fl - j * P.qm;   // f_{i + j Qm} = e_{i E/Qm + j}
-  const uint32_t nb = min(32u, P.g - f);
+  uint32_t e_r = r < P.rm.n_lo ? P.rm.e_lo : P.rm.e_hi, eq = r < P.rm.n_lo ? P.rm.eq_lo : P.rm.eq_hi;
+  uint32_t j = fl / P.rm.qm, i = fl - j * P.rm.qm;   // f_{i + j Qm} = e_{i E/Qm + j}
+  const uint32_t nb = min(32u, P.rm.g - f);
   uint32_t val = 0u;
   for (uint32_t b = 0; b < nb; ++b) {
     uint32_t k = i * eq + j, q;
-    if (P.rep) ce_divmod(k, P.prm, P.inv_prm, q, k);   // repetition wraps round the buffer
+    if (P.rep) ce_divmod(k, P.rm.p, P.inv_prm, q, k);   // repetition wraps round the buffer
     uint32_t rho = s + k;
-    if (rho >= P.prm) rho -= P.prm;
-    const uint32_t pos = (rho < P.f0 ? rho : rho + P.nf) + P.two_zc;
+    if (rho >= P.rm.p) rho -= P.rm.p;
+    const uint32_t pos = (rho < P.rm.f0 ? rho : rho + P.rm.nf) + P.two_zc;
     val |= ((word(r, pos >> 5) >> (31u - (pos & 31u))) & 1u) << (31u - b);
-    if (++i == P.qm) {
+    if (++i == P.rm.qm) {
       i = 0u;
       ++j;
     }
     if (++fl == e_r) {   // the next block's bits follow (5.5)
       ++r;
       fl = i = j = 0u;
-      e_r = r < P.n_lo ? P.e_lo : P.e_hi;
-      eq = r < P.n_lo ? P.eq_lo : P.eq_hi;
+      e_r = r < P.rm.n_lo ? P.rm.e_lo : P.rm.e_hi;
+      eq = r < P.rm.n_lo ? P.rm.eq_lo : P.rm.eq_hi;
     }
   }
   return val;
@@ -318,9 +311,9 @@ __global__ __launch_bounds__(ENC_NT) void ce_enc_kernel(EncDev P, const uint32_t
   __syncthreads();
 
   // ---- 5.4.2.1, 5.4.2.2, 5.5: the block's dwords of g ----
-  const uint32_t base = r < P.n_lo ? r * P.e_lo : P.base_hi + (r - P.n_lo) * P.e_hi, e_r = r < P.n_lo ? P.e_lo : P.e_hi;
+  const uint32_t base = r < P.rm.n_lo ? r * P.rm.e_lo : P.rm.base_hi + (r - P.rm.n_lo) * P.rm.e_hi, e_r = r < P.rm.n_lo ? P.rm.e_lo : P.rm.e_hi;
   const uint32_t d1 = r + 1u == P.c ? P.g_row_dwords : (base + e_r) >> 5;
-  const uint32_t s = enc_start(P, (uint32_t)rv[(int64_t)slot * rv_stride]);
+  const uint32_t s = ce_rm_walk_start(P, (uint32_t)rv[(int64_t)slot * rv_stride]);
   uint32_t* const grow = reinterpret_cast<uint32_t*>(g) + (size_t)slot * P.g_row_dwords;
   for (uint32_t d = (base >> 5) + t; d < d1; d += ENC_NT)
     grow[d] = __builtin_bswap32(enc_gather_dword(P, d, s, [&](uint32_t, uint32_t i) { return s_cw[i]; }));
@@ -332,7 +325,7 @@ __global__ __launch_bounds__(ENC_NT) void ce_enc_gather_kernel(EncDev P, const u
   const uint32_t slot = blockIdx.x / tiles_per_slot, tile = blockIdx.x - slot * tiles_per_slot;
   const uint32_t d = tile * ENC_NT + threadIdx.x;
   if (d >= P.g_row_dwords) return;
-  const uint32_t s = enc_start(P, (uint32_t)rv[(int64_t)slot * rv_stride]);
+  const uint32_t s = ce_rm_walk_start(P, (uint32_t)rv[(int64_t)slot * rv_stride]);
   const uint32_t* const cws = reinterpret_cast<const uint32_t*>(cw) + (size_t)slot * P.c * P.cw_row_dwords;
   reinterpret_cast<uint32_t*>(g)[(size_t)slot * P.g_row_dwords + d] =
       __builtin_bswap32(enc_gather_dword(P, d, s, [&](uint32_t r, uint32_t i) { return __builtin_bswap32(cws[r * P.cw_row_dwords + i]); }));
@@ -340,8 +333,9 @@ __global__ __launch_bounds__(ENC_NT) void ce_enc_gather_kernel(EncDev P, const u
 
 // ---- host derivation: integers only ----
 
-struct EncGraph {                  // what the kernel reads of the graph
-  std::vector<uint32_t> table;     // row_start | edges (col | shift << 8) | steps
+struct EncGraph {                  // what plan creation takes besides the view
+  std::vector<uint32_t> table;     // the kernel's part of the graph: row_start | edges (col | shift << 8) | steps
+  CeRateMatch rm;
 };
 
 int enc_derive(const ce_enc_desc* d, ce_enc_host_view* v, EncGraph* out) {
@@ -349,38 +343,24 @@ int enc_derive(const ce_enc_desc* d, ce_enc_host_view* v, EncGraph* out) {
   if (!out) out = &local;
   memset(v, 0, sizeof(*v));
   if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
-  ce_rm_desc rd{};
-  rd.abi_version = d->abi_version;
-  rd.device = d->device;
-  rd.base_graph = d->base_graph;
-  rd.tbs = d->tbs;
-  rd.qm = d->qm;
-  rd.n_layers = d->n_layers;
-  rd.g_bits = d->g_bits;
-  rd.format = CE_RM_I8;
-  rd.n_ref = d->n_ref;
-  rd.filler_llr = 127.0f;
-  ce_rm_host_view rm;
-  if (const int rc = ce_rm_derive_host(&rd, &rm); rc != CE_OK) return rc;   // its text stands
-  v->b = rm.b, v->k_cb = rm.k_cb, v->c = rm.c, v->b_prime = rm.b_prime, v->k_prime = rm.k_prime, v->k_b = rm.k_b;
-  v->zc = rm.zc, v->k = rm.k, v->n = rm.n, v->n_cb = rm.n_cb, v->f0 = rm.f0, v->f1 = rm.f1, v->p_rm = rm.p;
-  v->n_lo = rm.n_lo, v->e_lo = rm.e_lo, v->e_hi = rm.e_hi;
-  for (int i = 0; i < 4; ++i) v->k0[i] = rm.k0[i], v->s[i] = rm.s[i];
-  const CeCrcSelect crc = ce_crc_select(d->tbs, rm.c, rm.k_prime);
+  if (const int rc = ce_ratematch_derive(d->base_graph, d->tbs, d->qm, d->n_layers, d->g_bits, d->n_ref, &out->rm); rc != CE_OK) return rc;
+  ce_ratematch_view(out->rm, v);
+  v->p_rm = out->rm.p;
+  const CeCrcSelect crc = ce_crc_select(d->tbs, v->c, v->k_prime);
   v->l_tb = crc.l_tb, v->l_cb = crc.l_cb, v->p = crc.p, v->g_tb = crc.g_tb, v->g_cb = crc.g_cb;
   v->tb_row_bytes = crc.tb_row_bytes;
   v->g_row_bytes = 16 * ((d->g_bits + 127) / 128);
 
   // ---- the graph ----
-  const int32_t zc = rm.zc, n_rows = d->n_rows, n_cols = d->n_cols, n_sys = n_cols - n_rows;
+  const int32_t zc = v->zc, n_rows = d->n_rows, n_cols = d->n_cols, n_sys = n_cols - n_rows;
   const int32_t want_sys = d->base_graph == 1 ? 22 : 10, max_cols = d->base_graph == 1 ? 68 : 52;
   if (!d->row_start || !d->col || !d->shift) return ce_fail(CE_ERR_INVALID, "null graph arrays");
   if (n_rows < 4 || n_rows > CE_LDPC_MAX_ROWS) return ce_fail(CE_ERR_INVALID, "n_rows=%d outside 4..%d", n_rows, CE_LDPC_MAX_ROWS);
   if (n_sys != want_sys || n_cols > max_cols)
     return ce_fail(CE_ERR_INVALID, "base graph %d has n_sys = %d and at most %d columns; the graph given has n_sys = %d and %d columns", d->base_graph, want_sys,
                    max_cols, n_sys, n_cols);
-  if ((int64_t)(n_cols - 2) * zc < rm.n_cb)
-    return ce_fail(CE_ERR_INVALID, "a graph of %d columns is too short for the circular buffer: (n_cols - 2) Zc = %d < N_cb = %d", n_cols, (n_cols - 2) * zc, rm.n_cb);
+  if ((int64_t)(n_cols - 2) * zc < v->n_cb)
+    return ce_fail(CE_ERR_INVALID, "a graph of %d columns is too short for the circular buffer: (n_cols - 2) Zc = %d < N_cb = %d", n_cols, (n_cols - 2) * zc, v->n_cb);
   if (d->row_start[0] != 0) return ce_fail(CE_ERR_INVALID, "row_start[0]=%d must be 0", d->row_start[0]);
   for (int32_t r = 0; r < n_rows; ++r) {
     const int32_t deg = d->row_start[r + 1] - d->row_start[r];
@@ -458,14 +438,14 @@ int enc_derive(const ce_enc_desc* d, ce_enc_host_view* v, EncGraph* out) {
       if (core_at[j - 1][0] >= 0) steps[j][4 + steps[j][2]++] = 0u | (uint32_t)core_at[j - 1][0] << 8;
     }
   }
-  const int32_t cols_needed = (2 * zc + rm.n_cb + zc - 1) / zc;
+  const int32_t cols_needed = (2 * zc + v->n_cb + zc - 1) / zc;
   v->rows_needed = cols_needed - n_sys < 4 ? 4 : cols_needed - n_sys > n_rows ? n_rows : cols_needed - n_sys;
   v->col_dwords = (zc + 31) / 32;
   v->ext_dwords = (2 * zc + 32 + 31) / 32 + 1;
   v->cw_row_bytes = 16 * ((n_cols * zc + 127) / 128);
   // two blocks meet inside a dword of g where a prefix sum of the E_r is no multiple of 32
-  for (int32_t r = 1; r < rm.c; ++r) {
-    const int64_t base = r <= rm.n_lo ? (int64_t)r * rm.e_lo : (int64_t)rm.n_lo * rm.e_lo + (int64_t)(r - rm.n_lo) * rm.e_hi;
+  for (int32_t r = 1; r < v->c; ++r) {
+    const int64_t base = r <= v->n_lo ? (int64_t)r * v->e_lo : (int64_t)v->n_lo * v->e_lo + (int64_t)(r - v->n_lo) * v->e_hi;
     if (base % 32) v->cw_required = 1;
   }
   v->threads = ENC_NT;
@@ -541,12 +521,9 @@ extern "C" int ce_enc_plan_create(const ce_enc_desc* d, ce_enc_plan** out) {
   D.zc = (uint32_t)v.zc, D.n_sys = (uint32_t)v.n_sys, D.n_rows = (uint32_t)d->n_rows, D.w = (uint32_t)v.col_dwords, D.we = (uint32_t)v.ext_dwords;
   D.kd = ((uint32_t)v.k / 32u + 2u + 3u) / 4u * 4u;
   D.graph_dw = (uint32_t)graph.table.size();
-  D.qm = (uint32_t)d->qm, D.g = (uint32_t)d->g_bits, D.f0 = (uint32_t)v.f0, D.nf = (uint32_t)(v.f1 - v.f0), D.prm = (uint32_t)v.p_rm;
-  D.s0 = (uint32_t)v.s[0], D.s1 = (uint32_t)v.s[1], D.s2 = (uint32_t)v.s[2], D.s3 = (uint32_t)v.s[3];
-  D.n_lo = (uint32_t)v.n_lo, D.e_lo = (uint32_t)v.e_lo, D.e_hi = (uint32_t)v.e_hi;
-  D.eq_lo = D.e_lo / D.qm, D.eq_hi = D.e_hi / D.qm, D.base_hi = D.n_lo * D.e_lo;
-  D.rep = D.e_hi > D.prm ? 1u : 0u;
-  D.inv_prm = 1.0f / (float)D.prm;
+  D.rm = ce_rm_walk_dev(graph.rm, d->qm, d->g_bits);
+  D.rep = D.rm.e_hi > D.rm.p ? 1u : 0u;
+  D.inv_prm = 1.0f / (float)D.rm.p;
   D.two_zc = 2u * D.zc;
   // powers: x^(128 (255 - t)) for both polynomials
   std::vector<uint32_t>& T = graph.table;

@@ -21,6 +21,7 @@
 #include <memory>
 
 #include "ce_eq.h"
+#include "ce_remap.h"
 #include "ce_stage.h"
 
 namespace {
@@ -30,8 +31,8 @@ constexpr int EQ_CH = CE_EQ_CHUNK_SC;
 constexpr int EQ_RXROW = EQ_CH + 1;   // LDS row of one (port, symbol): padded so the transposed read spreads over the banks
 static_assert(EQ_CH % 12 == 0 && EQ_CH * CE_MAX_SYMBOLS <= 2 * EQ_NT, "two REs per thread cover a chunk");
 
-// per symbol: x = first subcarrier of the hop's PRBs | one past the last << 16, y = data mask | data REs per PRB << 16,
-// z = first output row, w unused.  No hop on the symbol: all zero.
+// per symbol (ce_remap_entry): x = first subcarrier of the hop's PRBs | one past the last << 16, y = data mask | data REs
+// per PRB << 16, z = first output row, w unused.  No hop on the symbol: all zero.
 struct EqDev {
   uint32_t n_sym, n_sc, n_elem;   // n_elem = EQ_CH * n_sym
   uint32_t sym_magic;             // floor(2^16 / n_sym) + 1: e / n_sym = (e * sym_magic) >> 16 for e < 2 * EQ_NT (host-checked)
@@ -313,41 +314,7 @@ int eq_derive(const ce_eq_desc* d, ce_eq_host_view* v) {
   memset(v, 0, sizeof(*v));
   for (int s = 0; s < CE_MAX_SYMBOLS; ++s) v->sym_hop[s] = -1;
   if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
-  if (d->n_layers < 1 || d->n_layers > CE_MAX_LAYERS) return ce_fail(CE_ERR_UNSUPPORTED, "n_layers=%d outside 1..%d", d->n_layers, CE_MAX_LAYERS);
-  if (d->n_hops < 1 || d->n_hops > CE_MAX_HOPS) return ce_fail(CE_ERR_INVALID, "n_hops=%d outside 1..2", d->n_hops);
-  if (d->n_prb_grid < 1 || 12 * d->n_prb_grid > CE_FFT_SIZE) return ce_fail(CE_ERR_UNSUPPORTED, "grid of %d PRB: 12*n_prb must be in 12..%d", d->n_prb_grid, CE_FFT_SIZE);
-  if (d->n_sym < 1 || d->n_sym > CE_MAX_SYMBOLS) return ce_fail(CE_ERR_INVALID, "n_sym=%d outside 1..%d", d->n_sym, CE_MAX_SYMBOLS);
-  for (int h = 0; h < d->n_hops; ++h) {
-    const ce_eq_hop_desc& hd = d->hop[h];
-    if (hd.reserved_re_mask > 0xFFFu) return ce_fail(CE_ERR_INVALID, "hop %d: reserved_re_mask=0x%x has bits above the 12 REs of a PRB", h, hd.reserved_re_mask);
-    if (hd.prb_start < 0 || hd.n_prbs < 1 || (int64_t)hd.prb_start + hd.n_prbs > d->n_prb_grid)
-      return ce_fail(CE_ERR_INVALID, "hop %d: PRBs %d..%lld outside the grid of %d PRB", h, hd.prb_start, (long long)hd.prb_start + hd.n_prbs - 1, d->n_prb_grid);
-    if (hd.start_symbol < 0 || hd.n_alloc_symbols < 1 || (int64_t)hd.start_symbol + hd.n_alloc_symbols > d->n_sym)
-      return ce_fail(CE_ERR_INVALID, "hop %d: symbols %d..%lld outside the grid of %d symbols", h, hd.start_symbol, (long long)hd.start_symbol + hd.n_alloc_symbols - 1, d->n_sym);
-    for (int s = hd.start_symbol; s < hd.start_symbol + hd.n_alloc_symbols; ++s) {
-      if (v->sym_hop[s] >= 0) return ce_fail(CE_ERR_UNSUPPORTED, "hops %d and %d share OFDM symbol %d", v->sym_hop[s], h, s);
-      v->sym_hop[s] = h;
-      v->data_mask[s] = hd.dmrs_symbols[s] ? (int32_t)(0xFFFu & ~(unsigned)hd.reserved_re_mask) : 0xFFF;
-      v->data_res_per_prb[s] = ce_popcount12((unsigned)v->data_mask[s]);
-    }
-  }
-  // output order: symbol ascending, subcarrier ascending.  Every data RE is walked through the kernel's row formula.
-  int64_t n = 0;
-  for (int s = 0; s < d->n_sym; ++s) {
-    v->first_row[s] = (int32_t)n;
-    if (v->sym_hop[s] < 0) continue;
-    const ce_eq_hop_desc& hd = d->hop[v->sym_hop[s]];
-    for (int q = hd.prb_start; q < hd.prb_start + hd.n_prbs; ++q)
-      for (int re = 0; re < 12; ++re)
-        if ((v->data_mask[s] >> re) & 1) {
-          const int64_t row = v->first_row[s] + (int64_t)(q - hd.prb_start) * v->data_res_per_prb[s] + ce_popcount12((unsigned)v->data_mask[s] & ((1u << re) - 1u));
-          if (row != n) return ce_fail(CE_ERR_UNSUPPORTED, "row formula gives %lld for data RE %lld", (long long)row, (long long)n);
-          ++n;
-        }
-  }
-  if (n < 1) return ce_fail(CE_ERR_INVALID, "the allocation has no data RE");
-  v->n_data_re = (int32_t)n;   // <= 4096 * 14
-  return CE_OK;
+  return ce_remap_derive(*d, v);   // every other check, and the output order: symbol ascending, subcarrier ascending
 }
 
 }  // namespace
@@ -380,9 +347,8 @@ extern "C" int ce_eq_plan_create(const ce_eq_desc* d, ce_eq_plan** out) {
   uint32_t sc_lo = P.n_sc, sc_hi = 0;
   for (int s = 0; s < d->n_sym; ++s) {
     if (v.sym_hop[s] < 0) continue;
-    const ce_eq_hop_desc& hd = d->hop[v.sym_hop[s]];
-    const uint32_t lo = 12u * (uint32_t)hd.prb_start, hi = lo + 12u * (uint32_t)hd.n_prbs;   // hi <= n_sc <= 4096
-    tab[s] = make_uint4(lo | (hi << 16), (uint32_t)v.data_mask[s] | ((uint32_t)v.data_res_per_prb[s] << 16), (uint32_t)v.first_row[s], 0u);
+    tab[s] = ce_remap_entry(v, s, d->hop[v.sym_hop[s]]);
+    const uint32_t lo = tab[s].x & 0xFFFFu, hi = tab[s].x >> 16;
     sc_lo = lo < sc_lo ? lo : sc_lo;
     sc_hi = hi > sc_hi ? hi : sc_hi;
   }

@@ -19,7 +19,8 @@
 //      words (v_alignbit) and forms the level by integer arithmetic; a pilot RE reads pilots[k][col][l] and scales it; all
 //      else is +0.  The two REs leave as one 16-byte store; lanes run along the subcarrier axis of one layer row.
 // No atomics, no scratch.  rnti / n_id only enter the unsigned arithmetic of c_init, the bits of g only arithmetic: every
-// address comes from the block index, the thread index and host-derived plan values.  Geometry and measurements: DESIGN 6m.
+// address comes from the block index, the thread index and host-derived plan values.  Which REs carry data, their rows and
+// the table entry that says so are ce_remap.h's, shared with the equalizer.  Geometry and measurements: DESIGN 6m.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,6 +32,7 @@
 
 #include "ce_gold.h"
 #include "ce_mod.h"
+#include "ce_remap.h"
 #include "ce_stage.h"
 
 namespace {
@@ -52,10 +54,11 @@ struct ModDev {
   uint32_t n_groups, pad0, pad1, pad2;       // n_groups: symbol groups per slot
 };
 
-// Per symbol (uint4): x = lo | hi << 16 (the hop's subcarriers [lo, hi); 0, 0 outside both hops), y = data_mask | data REs
-// per PRB << 16, z = first_row, w = re_mask[0] | re_mask[1] << 12 | pilot column << 24 | is DM-RS << 28.
+// Per symbol (uint4): x, y, z are the data-RE map's entry (ce_remap_entry: x = lo | hi << 16, the hop's subcarriers [lo, hi);
+// 0, 0 outside both hops; y = data_mask | data REs per PRB << 16, z = first_row), w = re_mask[0] | re_mask[1] << 12 |
+// pilot column << 24 | is DM-RS << 28.
 
-// Data REs of the allocation below subcarrier lo + d of a symbol.
+// Data REs of the allocation below subcarrier lo + d of a symbol (the host's ce_rows_before).
 __device__ __forceinline__ uint32_t mod_rows_before(uint32_t d, uint32_t dmask, uint32_t dpp) {
   const uint32_t q = d / 12u, r = d - 12u * q;
   return q * dpp + (uint32_t)__popc(dmask & ((1u << r) - 1u));
@@ -205,27 +208,14 @@ __global__ __launch_bounds__(MOD_NT) void ce_mod_kernel(ModDev P, const uint4* _
 
 // ---- host derivation: integers only ----
 
-int mod_rows_before_host(int d, int dmask, int dpp) { return (d / 12) * dpp + ce_popcount12((unsigned)dmask & ((1u << (d % 12)) - 1u)); }
-
 int mod_derive(const ce_mod_desc* d, ce_mod_host_view* v) {
   memset(v, 0, sizeof(*v));
   for (int s = 0; s < CE_MAX_SYMBOLS; ++s) v->sym_hop[s] = v->dmrs_col[s] = -1;
   if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
   if (d->qm != 2 && d->qm != 4 && d->qm != 6 && d->qm != 8) return ce_fail(CE_ERR_UNSUPPORTED, "qm=%d: modulation orders 2, 4, 6 and 8 are supported", d->qm);
   if (d->scramble != 0 && d->scramble != 1) return ce_fail(CE_ERR_INVALID, "scramble=%d is neither 0 nor 1", d->scramble);
-  ce_eq_desc eq;
-  memset(&eq, 0, sizeof(eq));
-  eq.abi_version = d->abi_version, eq.device = d->device, eq.n_prb_grid = d->n_prb_grid, eq.n_sym = d->n_sym;
-  eq.n_layers = d->n_layers, eq.n_hops = d->n_hops;
-  for (int h = 0; h < CE_MAX_HOPS; ++h) {
-    const ce_mod_hop_desc& hd = d->hop[h];
-    memcpy(eq.hop[h].dmrs_symbols, hd.dmrs_symbols, sizeof(hd.dmrs_symbols));
-    eq.hop[h].reserved_re_mask = hd.reserved_re_mask;
-    eq.hop[h].prb_start = hd.prb_start, eq.hop[h].n_prbs = hd.n_prbs;
-    eq.hop[h].start_symbol = hd.start_symbol, eq.hop[h].n_alloc_symbols = hd.n_alloc_symbols;
-  }
-  ce_eq_host_view ev;
-  if (const int rc = ce_eq_derive_host(&eq, &ev); rc != CE_OK) return rc;   // its text stands
+  CeReMap ev;   // the rows the equalizer writes: ce_remap.h
+  if (const int rc = ce_remap_derive(*d, &ev); rc != CE_OK) return rc;
   const int n_cdm = (d->n_layers + 1) / 2, ppp = ce_popcount12(d->hop[0].re_mask[0]);
   int col = 0;
   for (int h = 0; h < d->n_hops; ++h) {
@@ -287,8 +277,8 @@ int mod_derive(const ce_mod_desc* d, ce_mod_host_view* v) {
     for (int t = 0; t < v->tiles_per_symbol; ++t) {
       const int a0 = std::min(std::max(t * MOD_TILE, lo), hi), a1 = std::min(std::max((t + 1) * MOD_TILE, lo), hi);
       const int64_t per_row = (int64_t)d->n_layers * d->qm;
-      const int64_t bit0 = (ev.first_row[s] + mod_rows_before_host(a0 - lo, ev.data_mask[s], ev.data_res_per_prb[s])) * per_row;
-      const int64_t bit1 = (ev.first_row[s] + mod_rows_before_host(a1 - lo, ev.data_mask[s], ev.data_res_per_prb[s])) * per_row;
+      const int64_t bit0 = (ev.first_row[s] + ce_rows_before(a0 - lo, ev.data_mask[s], ev.data_res_per_prb[s])) * per_row;
+      const int64_t bit1 = (ev.first_row[s] + ce_rows_before(a1 - lo, ev.data_mask[s], ev.data_res_per_prb[s])) * per_row;
       if (bit1 > G) return ce_fail(CE_ERR_UNSUPPORTED, "symbol %d, tile %d ends at bit %lld of %lld", s, t, (long long)bit1, (long long)G);
       const int nblk = bit1 > bit0 ? (int)((bit1 - 1) / MOD_BLOCK_BITS - bit0 / MOD_BLOCK_BITS + 1) : 0;
       if (nblk > MOD_MAXB - 1) return ce_fail(CE_ERR_UNSUPPORTED, "symbol %d, tile %d touches %d Gold blocks: at most %d fit", s, t, nblk, MOD_MAXB - 1);
@@ -342,9 +332,8 @@ extern "C" int ce_mod_plan_create(const ce_mod_desc* d, ce_mod_plan** out) {
   for (int s = 0; s < d->n_sym; ++s) {
     if (v.sym_hop[s] < 0) continue;
     const ce_mod_hop_desc& hd = d->hop[v.sym_hop[s]];
-    const uint32_t lo = 12u * (uint32_t)hd.prb_start, hi = lo + 12u * (uint32_t)hd.n_prbs;   // hi <= n_sc <= 4096
-    const uint32_t dm = v.dmrs_col[s] < 0 ? 0u : (uint32_t)hd.re_mask[0] | ((d->n_layers > 2 ? (uint32_t)hd.re_mask[1] : 0u) << 12) | ((uint32_t)v.dmrs_col[s] << 24) | (1u << 28);
-    tab[s] = make_uint4(lo | (hi << 16), (uint32_t)v.data_mask[s] | ((uint32_t)v.data_res_per_prb[s] << 16), (uint32_t)v.first_row[s], dm);
+    tab[s] = ce_remap_entry(v, s, hd);
+    tab[s].w = v.dmrs_col[s] < 0 ? 0u : (uint32_t)hd.re_mask[0] | ((d->n_layers > 2 ? (uint32_t)hd.re_mask[1] : 0u) << 12) | ((uint32_t)v.dmrs_col[s] << 24) | (1u << 28);
   }
   CeDeviceScope scope(d->device);
   hipError_t e = ce_upload(scope.err, &p->symtab, tab, sizeof(tab));

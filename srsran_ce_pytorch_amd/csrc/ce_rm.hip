@@ -19,6 +19,7 @@
 // of the same cache lines are read by other workgroups of the same slot, so the workgroup-to-slot map keeps a slot on one
 // XCD (blockIdx & 7 is the XCD under round-robin dispatch: XCD x works through slots x, x + 8, ..), where the slot's row
 // (at most 8 MiB at the largest G in float32, 0.3 .. 1.3 MB at 273 PRB) stays in that XCD's L2 while its tiles run.
+// E_r, P, the fillers and the start ranks are ce_ratematch.h's, derived and laid out once for this kernel and the encoder's.
 // DESIGN 6g.
 //
 // The division of k by E_r/Qm is a float32 multiplication by a host-derived reciprocal with a correction of +-1: the
@@ -32,8 +33,8 @@
 #include <memory>
 #include <type_traits>
 
+#include "ce_ratematch.h"
 #include "ce_rm.h"
-#include "ce_segment.h"
 #include "ce_stage.h"
 
 namespace {
@@ -44,11 +45,8 @@ constexpr int RM_UPT = RM_TILE / RM_NT;   // units per thread
 static_assert(RM_TILE % RM_NT == 0, "a tile is whole units per thread");
 
 struct RmDev {
-  uint32_t n_cb, c, qm, g;        // N_cb, C, Qm, G
-  uint32_t f0, f1, nf, p;         // fillers [f0, f1), nf = f1 - f0, P = N_cb - nf
-  uint32_t s0, s1, s2, s3;        // per rv: the rank the walk starts at
-  uint32_t n_lo, e_lo, e_hi;      // E_r = e_lo for r < n_lo, e_hi otherwise
-  uint32_t eq_lo, eq_hi, base_hi; // E_r / Qm; base_hi = n_lo * e_lo, the first element of block n_lo
+  uint32_t n_cb, c, f1;           // N_cb, C, the fillers' end f0 + nf
+  RmWalkDev rm;
   float inv_eq_lo, inv_eq_hi;     // float32(1 / eq)
   uint32_t tiles_per_block;       // workgroups per code block
   uint32_t n_tiles;               // workgroups per slot = C * tiles_per_block
@@ -72,13 +70,12 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
   const uint32_t b = grp * 8u + xcd;
   if (b >= n_slots) return;
   const uint32_t r = w / P.tiles_per_block, tile = w - r * P.tiles_per_block;
-  const bool lo = r < P.n_lo;
-  const uint32_t e_r = lo ? P.e_lo : P.e_hi, eq = lo ? P.eq_lo : P.eq_hi;
+  const bool lo = r < P.rm.n_lo;
+  const uint32_t e_r = lo ? P.rm.e_lo : P.rm.e_hi, eq = lo ? P.rm.eq_lo : P.rm.eq_hi;
   const float inv = lo ? P.inv_eq_lo : P.inv_eq_hi;
-  const uint32_t base = lo ? r * P.e_lo : P.base_hi + (r - P.n_lo) * P.e_hi;
-  const El* __restrict__ const row = reinterpret_cast<const El*>(llr_) + (int64_t)b * P.g + base;   // f_0 .. f_{E_r - 1} of the block
-  const uint32_t rvb = (uint32_t)rv[(int64_t)b * rv_stride] & 3u;
-  const uint32_t s = rvb == 0 ? P.s0 : rvb == 1 ? P.s1 : rvb == 2 ? P.s2 : P.s3;
+  const uint32_t base = lo ? r * P.rm.e_lo : P.rm.base_hi + (r - P.rm.n_lo) * P.rm.e_hi;
+  const El* __restrict__ const row = reinterpret_cast<const El*>(llr_) + (int64_t)b * P.rm.g + base;   // f_0 .. f_{E_r - 1} of the block
+  const uint32_t s = ce_rm_walk_start(P, (uint32_t)rv[(int64_t)b * rv_stride]);
   const int64_t r0 = ((int64_t)b * P.c + r) * P.n_cb;   // the buffer's first element in the flat output
   const int64_t u0 = r0 / EPU;                          // its first unit (r0 >= 0), which holds `lead` elements of the buffer before
   const int32_t lead = (int32_t)(r0 - u0 * EPU);
@@ -110,9 +107,9 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
     const int32_t n0 = q[h] * EPU - lead;
     // (k, j, i) of the first non-filler position at or after the unit's first element inside the buffer
     const uint32_t nf = (uint32_t)max(n0, 0);
-    const uint32_t rank = nf < P.f0 ? nf : nf < P.f1 ? P.f0 : nf - P.nf;
-    uint32_t k = rank >= s ? rank - s : rank + P.p - s;
-    if (k >= P.p) k -= P.p;   // rank = P where the fillers run to the buffer's end (N_cb = K - 2 Zc): no position follows
+    const uint32_t rank = nf < P.rm.f0 ? nf : nf < P.f1 ? P.rm.f0 : nf - P.rm.nf;
+    uint32_t k = rank >= s ? rank - s : rank + P.rm.p - s;
+    if (k >= P.rm.p) k -= P.rm.p;   // rank = P where the fillers run to the buffer's end (N_cb = K - 2 Zc): no position follows
     uint32_t j, i;
     ce_divmod(k, eq, inv, j, i);
     k_first[h] = k;
@@ -120,17 +117,17 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
 #pragma unroll
     for (int32_t e = 0; e < EPU; ++e) {
       const uint32_t n = (uint32_t)(n0 + e);   // an element before the buffer wraps to a large value
-      const bool live = q[h] < n_units && n < P.n_cb && !(n >= P.f0 && n < P.f1);
+      const bool live = q[h] < n_units && n < P.n_cb && !(n >= P.rm.f0 && n < P.f1);
       const bool hit = live && k < e_r;
       hits[h] |= (hit ? 1u : 0u) << e;
-      first[h][e] = row[hit ? i * P.qm + j : 0u];   // e_k = f_{j + i Qm}: interleaver row j < Qm, column i < E_r / Qm
+      first[h][e] = row[hit ? i * P.rm.qm + j : 0u];   // e_k = f_{j + i Qm}: interleaver row j < Qm, column i < E_r / Qm
       if (I8 && live) {   // the next non-filler position's k
         ++k;
         if (++i == eq) {
           i = 0;
           ++j;
         }
-        if (k == P.p) k = i = j = 0;
+        if (k == P.rm.p) k = i = j = 0;
       }
     }
   }
@@ -147,22 +144,22 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
       if (n >= P.n_cb) continue;
       valid |= 1u << e;
       Acc acc;
-      if (n >= P.f0 && n < P.f1) {
+      if (n >= P.rm.f0 && n < P.f1) {
         acc = I8 ? (Acc)127 : (Acc)P.filler;
       } else {
         acc = I8 ? (Acc)(int32_t)(int8_t)(kept[h] >> (8 * e)) : (Acc)__uint_as_float(kept[h]);
         if (hits[h] >> e & 1u) {
           acc += (Acc)first[h][e];
-          if (e_r > P.p) {   // repetition: k + P, k + 2 P, ..
-            for (uint32_t k2 = k + P.p; k2 < e_r; k2 += P.p) {
+          if (e_r > P.rm.p) {   // repetition: k + P, k + 2 P, ..
+            for (uint32_t k2 = k + P.rm.p; k2 < e_r; k2 += P.rm.p) {
               uint32_t j2, i2;
               ce_divmod(k2, eq, inv, j2, i2);
-              acc += (Acc)row[i2 * P.qm + j2];
+              acc += (Acc)row[i2 * P.rm.qm + j2];
             }
           }
           if constexpr (I8) acc = min(max(acc, -127), 127);
         }
-        if (I8 && ++k == P.p) k = 0;
+        if (I8 && ++k == P.rm.p) k = 0;
       }
       word |= I8 ? ((uint32_t)(int32_t)acc & 0xFFu) << (8 * e) : __float_as_uint((float)acc);
     }
@@ -178,56 +175,18 @@ __global__ __launch_bounds__(RM_NT) void ce_rm_kernel(RmDev P, const void* __res
 
 // ---- host derivation: integers only ----
 
-int rm_derive(const ce_rm_desc* d, ce_rm_host_view* v) {
+int rm_derive(const ce_rm_desc* d, ce_rm_host_view* v, CeRateMatch* m) {
   memset(v, 0, sizeof(*v));
   if (d->abi_version != CE_ABI_VERSION) return ce_fail(CE_ERR_INVALID, "ABI version %d != %d", d->abi_version, CE_ABI_VERSION);
-  if (d->base_graph != 1 && d->base_graph != 2) return ce_fail(CE_ERR_INVALID, "base_graph=%d is neither 1 nor 2", d->base_graph);
-  if (d->qm != 2 && d->qm != 4 && d->qm != 6 && d->qm != 8) return ce_fail(CE_ERR_INVALID, "qm=%d: modulation orders 2, 4, 6 and 8 are supported", d->qm);
-  if (d->n_layers < 1 || d->n_layers > 4) return ce_fail(CE_ERR_INVALID, "n_layers=%d outside 1..4", d->n_layers);
   if (d->format != CE_RM_F32 && d->format != CE_RM_I8) return ce_fail(CE_ERR_INVALID, "format=%d is neither float32 (0) nor int8 (1)", d->format);
-  if (d->tbs < 1) return ce_fail(CE_ERR_INVALID, "tbs=%d must be positive", d->tbs);
   if (d->format == CE_RM_F32 && !(d->filler_llr > 0.0f && d->filler_llr < INFINITY)) return ce_fail(CE_ERR_INVALID, "filler_llr=%g must be positive and finite", (double)d->filler_llr);
-  if (d->n_ref < 0) return ce_fail(CE_ERR_INVALID, "n_ref=%d is negative", d->n_ref);
-  const bool bg1 = d->base_graph == 1;
-  CeSegment seg;   // 5.2.2 and the lifting size: shared with ce_tb
-  if (const int rc = ce_segment_derive(d->base_graph, d->tbs, &seg); rc != CE_OK) return rc;
-  const int64_t B = seg.b, K_cb = seg.k_cb, C = seg.c, Bp = seg.b_prime, Kp = seg.k_prime, K_b = seg.k_b, Zc = seg.zc, K = seg.k, N = seg.n;
-  if (d->n_ref != 0 && d->n_ref < K - 2 * Zc) return ce_fail(CE_ERR_INVALID, "n_ref=%d is below K - 2 Zc = %lld", d->n_ref, (long long)(K - 2 * Zc));
-  const int64_t N_cb = d->n_ref == 0 ? N : (N < d->n_ref ? N : (int64_t)d->n_ref);
-  const int64_t f0 = Kp - 2 * Zc, f1 = K - 2 * Zc, P = N_cb - (f1 - f0);
-  if (f0 < 0 || P < 1) return ce_fail(CE_ERR_INVALID, "tbs=%d: no transmittable position in the circular buffer", d->tbs);
-  const int64_t lq = (int64_t)d->n_layers * d->qm, G = d->g_bits;
-  if (G < 1 || G % lq != 0) return ce_fail(CE_ERR_INVALID, "g_bits=%d is no positive multiple of n_layers * qm = %lld", d->g_bits, (long long)lq);
-  if (G > CE_DEMOD_MAX_BITS) return ce_fail(CE_ERR_INVALID, "g_bits=%d: more than %d bits per slot", d->g_bits, CE_DEMOD_MAX_BITS);
-  const int64_t q = G / lq;
-  if (q < C) return ce_fail(CE_ERR_INVALID, "g_bits=%d: %lld symbols per layer for %lld code blocks", d->g_bits, (long long)q, (long long)C);
-  if (C * N_cb > CE_RM_MAX_SLOT_ELEMS) return ce_fail(CE_ERR_UNSUPPORTED, "%lld code blocks of %lld positions: more than %d outputs per slot", (long long)C, (long long)N_cb, CE_RM_MAX_SLOT_ELEMS);
-  v->b = (int32_t)B;
-  v->k_cb = (int32_t)K_cb;
-  v->c = (int32_t)C;
-  v->b_prime = (int32_t)Bp;
-  v->k_prime = (int32_t)Kp;
-  v->k_b = (int32_t)K_b;
-  v->zc = (int32_t)Zc;
-  v->k = (int32_t)K;
-  v->n = (int32_t)N;
-  v->n_cb = (int32_t)N_cb;
-  v->f0 = (int32_t)f0;
-  v->f1 = (int32_t)f1;
-  v->p = (int32_t)P;
-  v->n_lo = (int32_t)(C - q % C);
-  v->e_lo = (int32_t)(lq * (q / C));
-  v->e_hi = (int32_t)(lq * ((q + C - 1) / C));
-  const int num1[4] = {0, 17, 33, 56}, num2[4] = {0, 13, 25, 43};
-  for (int i = 0; i < 4; ++i) {
-    const int64_t k0 = (bg1 ? num1[i] : num2[i]) * N_cb / ((bg1 ? 66 : 50) * Zc) * Zc;
-    v->k0[i] = (int32_t)k0;
-    v->s[i] = (int32_t)(k0 < f0 ? k0 : k0 < f1 ? f0 : k0 - (f1 - f0));
-  }
+  if (const int rc = ce_ratematch_derive(d->base_graph, d->tbs, d->qm, d->n_layers, d->g_bits, d->n_ref, m); rc != CE_OK) return rc;
+  ce_ratematch_view(*m, v);
+  v->p = m->p;
   v->unit_elems = d->format == CE_RM_I8 ? 4 : 1;
   // a buffer starts up to unit_elems - 1 elements into its first unit
-  v->tiles_per_block = (int32_t)(((N_cb + 2 * (v->unit_elems - 1)) / v->unit_elems + RM_TILE - 1) / RM_TILE);
-  v->n_tiles = (int32_t)(C * v->tiles_per_block);
+  v->tiles_per_block = (int32_t)(((m->n_cb + 2 * (v->unit_elems - 1)) / v->unit_elems + RM_TILE - 1) / RM_TILE);
+  v->n_tiles = v->c * v->tiles_per_block;
   return CE_OK;
 }
 
@@ -242,13 +201,15 @@ struct ce_rm_plan {
 
 extern "C" int ce_rm_derive_host(const ce_rm_desc* d, ce_rm_host_view* v) {
   if (!d || !v) return ce_fail(CE_ERR_INVALID, "null argument");
-  return rm_derive(d, v);
+  CeRateMatch m;
+  return rm_derive(d, v, &m);
 }
 
 extern "C" int ce_rm_plan_create(const ce_rm_desc* d, ce_rm_plan** out) {
   if (!d || !out) return ce_fail(CE_ERR_INVALID, "null argument");
   ce_rm_host_view v;
-  if (const int rc = rm_derive(d, &v); rc != CE_OK) return rc;
+  CeRateMatch m;
+  if (const int rc = rm_derive(d, &v, &m); rc != CE_OK) return rc;
   auto p = ce_new_plan<ce_rm_plan>();
   if (!p) return ce_fail(CE_ERR_NOMEM, "out of host memory");
   p->device = d->device;
@@ -260,24 +221,10 @@ extern "C" int ce_rm_plan_create(const ce_rm_desc* d, ce_rm_plan** out) {
   RmDev& D = p->dev;
   D.n_cb = (uint32_t)v.n_cb;
   D.c = (uint32_t)v.c;
-  D.qm = (uint32_t)d->qm;
-  D.g = (uint32_t)d->g_bits;
-  D.f0 = (uint32_t)v.f0;
   D.f1 = (uint32_t)v.f1;
-  D.nf = (uint32_t)(v.f1 - v.f0);
-  D.p = (uint32_t)v.p;
-  D.s0 = (uint32_t)v.s[0];
-  D.s1 = (uint32_t)v.s[1];
-  D.s2 = (uint32_t)v.s[2];
-  D.s3 = (uint32_t)v.s[3];
-  D.n_lo = (uint32_t)v.n_lo;
-  D.e_lo = (uint32_t)v.e_lo;
-  D.e_hi = (uint32_t)v.e_hi;
-  D.eq_lo = (uint32_t)(v.e_lo / d->qm);
-  D.eq_hi = (uint32_t)(v.e_hi / d->qm);
-  D.base_hi = (uint32_t)v.n_lo * (uint32_t)v.e_lo;
-  D.inv_eq_lo = 1.0f / (float)D.eq_lo;
-  D.inv_eq_hi = 1.0f / (float)D.eq_hi;
+  D.rm = ce_rm_walk_dev(m, d->qm, d->g_bits);
+  D.inv_eq_lo = 1.0f / (float)D.rm.eq_lo;
+  D.inv_eq_hi = 1.0f / (float)D.rm.eq_hi;
   D.tiles_per_block = (uint32_t)v.tiles_per_block;
   D.n_tiles = (uint32_t)v.n_tiles;
   D.filler = d->filler_llr;

@@ -1,17 +1,12 @@
 // What the stages around the estimator (ce_dmrs, ce_eq, ce_demod, ce_rm, ce_denoise) share on the host: the steps of plan
 // creation and of a launch that do not depend on the stage.  Plain functions, called where the stage's own code was.
+// What two stages derive alike has a header of its own: ce_remap.h (the data-RE map), ce_ratematch.h (rate matching),
+// ce_segment.h, ce_gold.h, ce_crc.h, ce_fft.h.
 #pragma once
 #include <memory>
 #include <new>
 
 #include "ce_plan.h"
-
-// REs set in the 12-bit mask of a PRB (the equalizer's and the modulator's derivations).
-inline int ce_popcount12(unsigned m) {
-  int n = 0;
-  for (int r = 0; r < 12; ++r) n += (m >> r) & 1u;
-  return n;
-}
 
 // A default-constructed plan, or null (the caller reports CE_ERR_NOMEM).
 template <class Plan>
