@@ -1,6 +1,7 @@
 """MI355X-native PUSCH DM-RS channel estimator (batched, HIP kernels behind a C ABI)."""
 from .config import EstimatorConfig, HopConfig, empty_hop  # noqa: F401
 from .deprecode import PuschTransformDeprecoder  # noqa: F401
+from .dmrs import PuschLowPaprDmrs  # noqa: F401
 from .encoder import PuschTransportEncoder  # noqa: F401
 from .ldpc import LdpcGraph, PuschLdpcDecoder  # noqa: F401
 from .modulator import PuschModulator  # noqa: F401

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ofdm.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_dmrs_lp.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ofdm.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 
 
@@ -109,6 +109,8 @@ REGISTRY["ce_denoise.h"] = Header(structs={}, signatures={   # extension
     "ce_denoise_batch": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
 })
 CE_DMRS_MAX_WORDS, CE_DMRS_MAX_RE = 136, 2048
+CE_DMRS_LP_HOP_NEITHER, CE_DMRS_LP_HOP_GROUP, CE_DMRS_LP_HOP_SEQUENCE, CE_DMRS_LP_MAX_WORDS, CE_DMRS_LP_INFO_LEN = 0, 1, 2, 560, 8
+CE_DMRS_LP_FORM_ZC, CE_DMRS_LP_FORM_30, CE_DMRS_LP_FORM_PHI = 0, 1, 2
 
 
 class DmrsHopDesc(C.Structure):
@@ -142,6 +144,12 @@ REGISTRY["ce_dmrs.h"] = Header(structs={"ce_dmrs_hop_desc": DmrsHopDesc, "ce_dmr
     "ce_dmrs_plan_destroy": (None, [_vp]),
     "ce_dmrs_plan_get_info": (_int, [_vp, _P(DmrsInfo)]),
     "ce_dmrs_generate": (_int, [_vp, _vp, _vp, _vp, _i64p, _i64, _vp, _vp]),
+    # low-PAPR (Zadoff-Chu) DM-RS: scalars and pointers only, the host view goes out through caller-provided arrays
+    "ce_dmrs_lp_derive_host": (_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ce_dmrs_lp_copy_twiddles": (_int, [_i32, _vp]),
+    "ce_dmrs_lp_plan_create": (_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _P(_vp)]),
+    "ce_dmrs_lp_plan_destroy": (None, [_vp]),
+    "ce_dmrs_lp_generate": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
 })
 CE_EQ_MAX_PORTS, CE_EQ_CHUNK_SC = 8, 36
 
