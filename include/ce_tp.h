@@ -4,7 +4,7 @@
  * into the per-symbol one the demapper needs.  Behind it, further down: transform precoding, the forward direction
  * (ce_tp_precode), OFDM demodulation, samples to the resource grid (ce_ofdm_*), which runs the same passes over the
  * same host view at the lengths 128 .. 4096, and OFDM modulation, the grid to samples, on the demodulator's plan
- * (ce_ofdmtx_modulate).
+ * (ce_ofdmtx_modulate), and between those two the time-domain channel emulator (ce_chan_apply).
  *
  * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
  * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
@@ -240,6 +240,56 @@ int ce_ofdm_demodulate(const ce_ofdm_plan* plan, const void* samples, int64_t sl
  */
 int ce_ofdmtx_modulate(const ce_ofdm_plan* plan, const void* grid, int64_t n_slots, int64_t n_ports, void* samples,
                        int64_t slot_stride, int64_t port_stride, void* stream);
+
+/*
+ * TIME-DOMAIN CHANNEL EMULATOR between ce_ofdmtx_modulate and ce_ofdm_demodulate: a FIR channel from n_tx transmit to n_rx
+ * receive ports, a carrier frequency offset from a numerically controlled oscillator, and seeded white Gaussian noise, in
+ * ONE launch on `stream` of the CURRENT device, without a plan.  Scalars and pointers only.  For slot b < n_slots = B, receive
+ * port r < n_rx = R, sample t < n_samples = T, with P = n_tx, K = n_taps (the float64 operator of tests/chan_oracle.py
+ * `apply_ref`):
+ *     y[b][r][t] = exp(j 2 pi w_b(t) / 2^32) sum_{p<P} sum_{k<K} h[b][r][p][k] x[b][p][t - k]  +  sigma_b n[b][r][t]
+ * with x[b][p][t - k] = 0 for t - k < 0: every slot row is convolved on its own (np.convolve(..)[:T]), the tail of slot b does
+ * not run into slot b + 1.
+ *   CFO    w_b(t) = (phase0_b + fcw_b t) mod 2^32 in uint32 arithmetic, t counted from the row's start: fcw is an int32
+ *          frequency in units of 2^-32 cycles per sample (+-half the sample rate), phase0 a uint32.  The phase word is exact;
+ *          the kernel turns it into a phasor as sincospi(float32(int32(w)) 2^-31).  fcw == NULL: no rotation at all.
+ *   noise  n has unit power E|n|^2 = 1 and comes from Philox4x32-10 (multipliers D2511F53, CD9E8D57, Weyl constants
+ *          9E3779B9, BB67AE85) with the key (seed & 0xffffffff, seed >> 32) and the counter
+ *          (t >> 1, r, s & 0xffffffff, s >> 32), s = first_slot + b: one call gives the four words of the samples 2 i and
+ *          2 i + 1, (w0, w1) for 2 i and (w2, w3) for 2 i + 1.  Of a word pair (a, c): u1 = ((a >> 8) + 1) 2^-24 in (0, 1],
+ *          u2 = (c >> 8) 2^-24, n = sqrt(-ln u1) exp(j 2 pi u2).  So the noise of a sample depends on (seed, first_slot + b,
+ *          r, t) alone: not on the batch, the launch geometry, x or h.  sigma == NULL: no noise and no Philox call.
+ *
+ *  x        complex64 [slot][tx port][>= T], the last dimension contiguous, x_slot_stride and x_port_stride in complex
+ *           elements, any values >= 0 (a view into a longer stream, what ce_ofdmtx_modulate writes); 8-byte aligned, read with
+ *           8-byte loads.  Only [0, T) of each row is read.
+ *  taps     complex64 [slot][R][P][K], dense behind taps_slot_stride (complex elements): >= R P K, or 0 for one channel for
+ *           the whole batch.  8-byte aligned.
+ *  fcw, phase0, sigma   DEVICE memory, one int32 / uint32 / float32 per slot at b stride; stride 0: one value for the batch.
+ *           phase0 is read only where fcw is given.  sigma >= 0.
+ *  y        complex64, row (b, r) at b y_slot_stride + r y_port_stride; 8-byte aligned, written with 8-byte stores.  Every
+ *           sample of [0, T) of every row is written exactly once, nothing else.
+ * Asynchronous; n_slots == 0 launches nothing.  One 256-thread workgroup per (slot, rx port, tile of 1024 samples) stages
+ * the tile and its n_taps - 1 predecessors of every tx port in LDS (at most 40 KiB).  float32 arithmetic (restated in
+ * tests/chan_oracle.py `apply_f32`): FMAs in the fixed order p outer, k inner, per product re += h.re x.re,
+ * re -= h.im x.im, im += h.re x.im, im += h.im x.re; then the phasor (c, s): (fma(re, c, -(im s)), fma(re, s, im c)); then
+ * fma(sigma, n.re, .) and fma(sigma, n.im, .) with n = (rad cos, rad sin), rad = sqrtf(-logf(u1)), sincospi(2 u2).  No
+ * atomics, no scratch; every address and bound comes from the block index, the thread index and the scalars of the call.
+ * A NaN in x[b][p][t] reaches y[b][:][t .. t + K - 1] and nothing else.
+ * CE_ERR_INVALID: abi_version != CE_ABI_VERSION; n_tx outside 1..4, n_taps outside 1..128, n_rx < 1, n_samples < 1; a
+ * negative count or stride; a null x, y or taps (or fcw without phase0) in a non-empty batch; x, y or taps not 8-byte
+ * aligned; strides whose extent exceeds the address space; a taps_slot_stride between 1 and R P K - 1; rows of y that are
+ * not pairwise disjoint (ce_ofdmtx_modulate's conditions on its samples); the extent of y overlapping that of x or of taps.
+ * CE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups in one launch.
+ */
+int ce_chan_apply(int32_t abi_version, const void* x, int64_t x_slot_stride, int64_t x_port_stride, int64_t n_slots, int32_t n_tx,
+                  int64_t n_rx, int64_t n_samples, const void* taps, int64_t taps_slot_stride, int32_t n_taps, const int32_t* fcw,
+                  int64_t fcw_stride, const uint32_t* phase0, int64_t phase0_stride, const float* sigma, int64_t sigma_stride,
+                  uint64_t seed, int64_t first_slot, void* y, int64_t y_slot_stride, int64_t y_port_stride, void* stream);
+
+/* Host only: the four Philox words of the sample pair t_pair = t >> 1 of (slot = first_slot + b, rx port), as the kernel
+ * draws them: counter (t_pair, port, slot low, slot high), each truncated to 32 bits, key (seed low, seed high). */
+int ce_chan_noise_words(uint64_t seed, int64_t slot, int32_t port, int64_t t_pair, uint32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """MI355X-native PUSCH DM-RS channel estimator (batched, HIP kernels behind a C ABI)."""
 from .config import EstimatorConfig, HopConfig, empty_hop  # noqa: F401
+from .channel import PuschChannelEmulator, cfo_word, taps_from_delays  # noqa: F401
 from .deprecode import PuschTransformDeprecoder  # noqa: F401
 from .dmrs import PuschLowPaprDmrs  # noqa: F401
 from .encoder import PuschTransportEncoder  # noqa: F401

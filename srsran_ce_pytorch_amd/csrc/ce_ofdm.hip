@@ -174,16 +174,8 @@ int ofdm_derive(int32_t n_fft, int32_t n_prb_grid, int32_t n_sym, const int32_t*
 // What both launches check about a non-empty batch behind their pointers: the workgroup count, into *n_wg, and that the
 // extent of the strided tensor, in bytes, stays inside 64 bits.
 int ofdm_batch(const FftDev& f, int64_t n_slots, int64_t n_ports, int64_t slot_stride, int64_t port_stride, int64_t* n_wg) {
-  const int64_t lim = 0x7FFFFFFFll;
-  if (n_slots > lim || n_ports > lim || n_slots * n_ports > lim / (int64_t)f.wg_per_item)
-    return ce_fail(CE_ERR_UNSUPPORTED, "%lld slots x %lld ports of %u workgroups: more than 2^31-1 workgroups in one launch", (long long)n_slots,
-                   (long long)n_ports, f.wg_per_item);
-  *n_wg = n_slots * n_ports * (int64_t)f.wg_per_item;
-  const int64_t room = INT64_MAX >> 6;   // n_slots, n_ports < 2^31 here
-  if (slot_stride > room / n_slots || port_stride > room / n_ports)
-    return ce_fail(CE_ERR_INVALID, "slot_stride=%lld and port_stride=%lld: the extent of %lld slots x %lld ports exceeds the address space",
-                   (long long)slot_stride, (long long)port_stride, (long long)n_slots, (long long)n_ports);
-  return CE_OK;
+  if (const int rc = ce_rows_workgroups(n_slots, n_ports, (int64_t)f.wg_per_item, n_wg); rc != CE_OK) return rc;
+  return ce_rows_extent(n_slots, n_ports, slot_stride, port_stride);   // n_slots, n_ports < 2^31 here
 }
 
 }  // namespace
@@ -292,11 +284,7 @@ extern "C" int ce_ofdmtx_modulate(const ce_ofdm_plan* p, const void* grid, int64
   // every sample is written by one workgroup only: the rows of T samples pairwise disjoint, the ports inside a slot or the
   // slots inside a port (one continuous stream per port)
   const int64_t T = p->n_samples;
-  const bool port_inner = (n_ports == 1 || port_stride >= T) && (n_slots == 1 || slot_stride >= (n_ports - 1) * port_stride + T);
-  const bool slot_inner = (n_slots == 1 || slot_stride >= T) && (n_ports == 1 || port_stride >= (n_slots - 1) * slot_stride + T);
-  if (!port_inner && !slot_inner)
-    return ce_fail(CE_ERR_INVALID, "slot_stride=%lld and port_stride=%lld: the rows of %lld samples of %lld slots x %lld ports overlap",
-                   (long long)slot_stride, (long long)port_stride, (long long)T, (long long)n_slots, (long long)n_ports);
+  if (const int rc = ce_rows_disjoint(n_slots, n_ports, slot_stride, port_stride, T); rc != CE_OK) return rc;
   const uintptr_t g0 = reinterpret_cast<uintptr_t>(grid), s0 = reinterpret_cast<uintptr_t>(samples);
   const uintptr_t g1 = g0 + 8u * (uintptr_t)(n_slots * n_ports) * D.f.n_rows * D.n_sc;
   const uintptr_t s1 = s0 + 8u * (uintptr_t)((n_slots - 1) * slot_stride + (n_ports - 1) * port_stride + T);
