@@ -4,7 +4,8 @@
  * into the per-symbol one the demapper needs.  Behind it, further down: transform precoding, the forward direction
  * (ce_tp_precode), OFDM demodulation, samples to the resource grid (ce_ofdm_*), which runs the same passes over the
  * same host view at the lengths 128 .. 4096, and OFDM modulation, the grid to samples, on the demodulator's plan
- * (ce_ofdmtx_modulate), and between those two the time-domain channel emulator (ce_chan_apply).
+ * (ce_ofdmtx_modulate), between those two the time-domain channel emulator (ce_chan_apply), and the other front door, fronthaul
+ * I/Q (de)compression between the wire format of an O-RAN 7.2x radio unit and the grid's rows (ce_fh_*).
  *
  * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
  * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
@@ -290,6 +291,65 @@ int ce_chan_apply(int32_t abi_version, const void* x, int64_t x_slot_stride, int
 /* Host only: the four Philox words of the sample pair t_pair = t >> 1 of (slot = first_slot + b, rx port), as the kernel
  * draws them: counter (t_pair, port, slot low, slot high), each truncated to 32 bits, key (seed low, seed high). */
 int ce_chan_noise_words(uint64_t seed, int64_t slot, int32_t port, int64_t t_pair, uint32_t out[4]);
+
+/*
+ * FRONTHAUL I/Q (DE)COMPRESSION, the front door behind an O-RAN 7.2x radio unit, which does the FFT itself: the
+ * frequency-domain I/Q of one (port, symbol) as it travels (O-RAN.WG4.CUS Annex A.1 and the udCompParam byte) to and from
+ * rows of the resource grid, each direction in ONE launch on `stream` of the CURRENT device, without a plan.  Scalars and
+ * pointers only.  Every output is defined to the bit (restated bit-serially in tests/fh_oracle.py).
+ *
+ * A row carries n_prb PRBs one after the other without padding, row_bytes = n_prb prb_bytes in all (ce_fh_row_bytes).
+ *   CE_FH_BFP, mantissa width W = iq_width in 1..16: prb_bytes = 1 + 3 W.  Byte 0 is the compression parameter: its low 4
+ *       bits the exponent e in 0..15, its high 4 bits reserved (ignored by the decompressor, 0 from the compressor).  Then
+ *       the 24 mantissas I0, Q0, I1, Q1, .., I11, Q11, each W bits of two's complement, packed MSB first without gaps: bit 7
+ *       of byte 1 is the top bit of I0.
+ *   CE_FH_NONE: prb_bytes = 48, the 24 values as big-endian int16 in the same order and no parameter byte -- CE_FH_BFP with
+ *       W = 16, e = 0 and no byte 0.  iq_width must still lie in 1..16 and is otherwise ignored.
+ * Decompression: v = sign_extend(mantissa) << e as int32 (|v| <= 2^30 with at most 16 significant bits, so float(v) is
+ * exact); the component is float(v) * scale, one float32 multiply.
+ * Compression of a float32 component x: q = x * inv_scale (one float32 multiply; the caller passes
+ * inv_scale = float32(1 / double(scale))), v = rintf(q) to the nearest even, NaN -> 0, saturated to -32768 .. 32767 (the
+ * infinities saturate).  Per PRB, over its 24 values: mag = v >= 0 ? v : ~v, L = bit_length(max mag) (0 for 0),
+ * e = max(L + 1 - W, 0), mantissa = v >> e, an arithmetic shift (a floor); CE_FH_NONE stores v.  Hence e <= 15, every
+ * mantissa fits W bits, 0 <= v - (mantissa << e) < 2^e, and compressing mantissa << e gives (e, mantissa) again.
+ * scale and inv_scale: float32 in 2^-96 .. 2^96 (no product is denormal or overflows).
+ *
+ *  payload  uint8, row (b, r, y) at b slot + r port + y symbol stride, strides in BYTES; the base and the three strides
+ *           multiples of 4.  Read (ce_fh_decompress) with dword loads except a row's last row_bytes mod 4 bytes, which are
+ *           read one by one: no byte behind row_bytes is touched.  Written (ce_fh_compress) with dword stores and byte
+ *           stores for that tail: bytes between row_bytes and the next row are NOT written.
+ *  grid     complex64, 8-byte aligned: the first RE of the first PRB of row (0, 0, 0); row (b, r, y) at b slot + r port +
+ *           y symbol stride, strides in complex64 elements (any parity), subcarriers contiguous -- the estimator's fast
+ *           layout [slot][port][symbol][subcarrier], of which a PRB range is a section.  The 12 n_prb REs of every row are
+ *           written (read) exactly once, nothing else; 16-byte accesses where the base and the strides keep every row on
+ *           16 bytes, 8-byte accesses otherwise.
+ * One 256-thread workgroup per (slot, port, symbol, tile of 64 PRBs); at most 3.3 KiB of LDS.  No atomics, no scratch;
+ * payload and grid values enter arithmetic only: every address and bound comes from the block index, the thread index
+ * and the scalars of the call.  Asynchronous; n_slots == 0 launches nothing, whatever the pointers.
+ * CE_ERR_INVALID: abi_version != CE_ABI_VERSION; iq_width outside 1..16; n_prb outside 1..341; n_sym < 1; n_ports < 1;
+ * n_slots < 0; a scale outside 2^-96 .. 2^96 or not finite; a null pointer in a non-empty batch; a negative stride; a
+ * payload base or stride that is no multiple of 4; a grid that is not 8-byte aligned; strides whose extent exceeds the
+ * address space; rows of the WRITTEN side that are not pairwise disjoint (accepted: by ascending stride, each stride of a
+ * dimension with more than one entry at least the extent of everything inside it -- any nesting of slot, port and symbol;
+ * the strides of the side that is read are free, 0 repeats a row); the extents of payload and grid overlapping.
+ * CE_ERR_UNSUPPORTED: an unknown method; more than 2^31 - 1 workgroups in one launch.
+ */
+#define CE_FH_NONE 0
+#define CE_FH_BFP 1
+#define CE_FH_MAX_PRBS 341
+
+/* Host only: the bytes of a row of n_prb PRBs, n_prb (1 + 3 iq_width) or 48 n_prb, into *bytes. */
+int ce_fh_row_bytes(int32_t method, int32_t iq_width, int32_t n_prb, int64_t* bytes);
+
+int ce_fh_decompress(int32_t abi_version, const void* payload, int64_t payload_slot_stride, int64_t payload_port_stride,
+                     int64_t payload_symbol_stride, void* grid, int64_t grid_slot_stride, int64_t grid_port_stride,
+                     int64_t grid_symbol_stride, int64_t n_slots, int64_t n_ports, int32_t n_sym, int32_t n_prb, int32_t method,
+                     int32_t iq_width, float scale, void* stream);
+
+int ce_fh_compress(int32_t abi_version, void* payload, int64_t payload_slot_stride, int64_t payload_port_stride,
+                   int64_t payload_symbol_stride, const void* grid, int64_t grid_slot_stride, int64_t grid_port_stride,
+                   int64_t grid_symbol_stride, int64_t n_slots, int64_t n_ports, int32_t n_sym, int32_t n_prb, int32_t method,
+                   int32_t iq_width, float inv_scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ from .channel import PuschChannelEmulator, cfo_word, taps_from_delays  # noqa: F
 from .deprecode import PuschTransformDeprecoder  # noqa: F401
 from .dmrs import PuschLowPaprDmrs  # noqa: F401
 from .encoder import PuschTransportEncoder  # noqa: F401
+from .fronthaul import PuschFronthaulCompressor, PuschFronthaulDecompressor, bfp_pack, bfp_unpack  # noqa: F401
 from .ldpc import LdpcGraph, PuschLdpcDecoder  # noqa: F401
 from .modulator import PuschModulator  # noqa: F401
 from .ofdm import PuschOfdmDemodulator, PuschOfdmModulator  # noqa: F401

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_dmrs_lp.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ofdm.hip", "ce_chan.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_dmrs_lp.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ofdm.hip", "ce_chan.hip", "ce_fh.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 
 
@@ -274,7 +274,12 @@ REGISTRY["ce_tp.h"] = Header(structs={"ce_tp_desc": TpDesc, "ce_tp_info": TpInfo
     "ce_chan_apply": (_int, [_i32, _vp, _i64, _i64, _i64, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64,
                              C.c_uint64, _i64, _vp, _i64, _i64, _vp]),
     "ce_chan_noise_words": (_int, [C.c_uint64, _i64, _i32, _i64, _P(C.c_uint32)]),
+    # fronthaul I/Q (de)compression: no plan, scalars and pointers only
+    "ce_fh_row_bytes": (_int, [_i32, _i32, _i32, _i64p]),
+    "ce_fh_decompress": (_int, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, C.c_float, _vp]),
+    "ce_fh_compress": (_int, [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, C.c_float, _vp]),
 })
+CE_FH_NONE, CE_FH_BFP, CE_FH_MAX_PRBS = 0, 1, 341
 CE_LDPC_MAX_ZC, CE_LDPC_MAX_ROWS, CE_LDPC_MAX_COLS, CE_LDPC_MAX_ROW_DEGREE = 384, 46, 68, 19
 CE_LDPC_L_BOUND, CE_LDPC_LDS_MAX, CE_LDPC_F32, CE_LDPC_I8 = 4497, 163840, 0, 1
 CE_LDPC_STATE_IDX_SHIFT, CE_LDPC_STATE_MAG_SHIFT = 19, 24
