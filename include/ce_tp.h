@@ -5,7 +5,8 @@
  * (ce_tp_precode), OFDM demodulation, samples to the resource grid (ce_ofdm_*), which runs the same passes over the
  * same host view at the lengths 128 .. 4096, and OFDM modulation, the grid to samples, on the demodulator's plan
  * (ce_ofdmtx_modulate), between those two the time-domain channel emulator (ce_chan_apply), and the other front door, fronthaul
- * I/Q (de)compression between the wire format of an O-RAN 7.2x radio unit and the grid's rows (ce_fh_*).
+ * I/Q (de)compression between the wire format of an O-RAN 7.2x radio unit and the grid's rows (ce_fh_*), and behind that door
+ * PRACH preamble detection over such rows (ce_prach_*), on the same passes.
  *
  * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
  * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
@@ -350,6 +351,90 @@ int ce_fh_compress(int32_t abi_version, void* payload, int64_t payload_slot_stri
                    int64_t payload_symbol_stride, const void* grid, int64_t grid_slot_stride, int64_t grid_port_stride,
                    int64_t grid_symbol_stride, int64_t n_slots, int64_t n_ports, int32_t n_sym, int32_t n_prb, int32_t method,
                    int32_t iq_width, float inv_scale, void* stream);
+
+/*
+ * PRACH PREAMBLE DETECTION over frequency-domain rows, the other kind of uplink I/Q an O-RAN 7.2x radio unit sends (section
+ * type 3): per PRACH occasion and Zadoff-Chu root the correlation with the root in the frequency domain, an inverse transform
+ * of length N with the transforms' Stockham passes, the power delay profile summed over ports and repetitions, and per
+ * cyclic-shift window its maximum and where it lies.  Short formats (L_RA = 139, also 571 and 1151) and long formats
+ * (L_RA = 839) alike; the 1.25 kHz time-domain front end (decimation, long FFT) stays with the radio unit.  The entry points
+ * take scalars and pointers only; the one structure is ce_tp_host_view, which describes the N-point transform as it stands
+ * (m_sc holds N, n_workgroups_per_slot is 1: one workgroup per (occasion, root)).
+ *
+ * Plan values:
+ *     l_ra = L             139, 571, 839 or 1151 (odd primes)
+ *     n_fft = N            256, 512, 1024, 2048 or 4096, N > L
+ *     n_roots, roots[]     1 .. 64 distinct PHYSICAL root indices u_i in 1 .. L - 1 (host int32, read during the call).  The
+ *                          logical-to-physical table of TS 38.211 Tables 6.3.3.1-3/-4 is the caller's data.
+ *     n_cs                 0 .. L - 1, the cyclic-shift step N_CS (unrestricted set)
+ *     n_shifts             1 .. 64 windows per root, n_shifts n_cs <= L; n_cs = 0 requires n_shifts = 1
+ *     combine              0: repetitions are combined non-coherently, 1: coherently
+ * Derived on the host, in integers: the guard g = ceil(N / L); the shift C_v = v n_cs, v < n_shifts; for n_cs > 0
+ *     win_start[v] = (floor(((L - C_v) mod L) N / L) - g) mod N        win_len = floor(n_cs N / L)
+ * and for n_cs = 0 win_start[0] = 0, win_len = N.  The windows are pairwise disjoint (floor(x) - floor(x - y) >= floor(y));
+ * window 0 always wraps round N.  A preamble of shift C_v that arrives without delay peaks at the fractional index
+ * ((L - C_v) mod L) N / L; the guard keeps the main lobe of such a preamble out of the tail of the neighbouring window.
+ *
+ * Root table, TS 38.211 6.3.3.1: x_u(n) = exp(-j 2 pi ((u n (n + 1) / 2) mod L) / L), the index reduced in integers;
+ * X_u[k] = sum_{n<L} x_u(n) exp(-j 2 pi n k / L); T_i[k] = conj(X_{u_i}[k]) / |X_{u_i}[k]|, k < L, in double on the host and
+ * rounded once to float32.  (For odd prime L, X_u[k] = X_u[0] conj(x_u(u^-1 k mod L)): the host takes the sum once per root.)
+ *
+ * Per occasion b and root i a TERM is (port r, repetition s) with Z[k] = Y[b][r][s][k] T_i[k] when combine = 0, and a port r
+ * with Z[k] = (sum_s Y[b][r][s][k]) T_i[k], summed over s ascending, when combine = 1.  Then, for n < N:
+ *     z[n]           = (1 / L) sum_{k<L} Z[k] exp(+j 2 pi k n / N)         (bin k -> k, the other N - L bins zero)
+ *     P[b][i][n]     = sum over the terms of |z[n]|^2
+ *     mean[b][i]     = (1 / N) sum_n P[b][i][n]
+ *     peak[b][i][v]  = max_{d < win_len} P[b][i][(win_start[v] + d) mod N]
+ *     delay[b][i][v] = the smallest d that attains it
+ * A noiseless preamble of amplitude a on one port, aligned to the N grid, gives peak = a^2.  Detection is
+ * peak / mean > threshold and belongs to the caller.  Preamble (i, v) arrived
+ * (win_start[v] + delay - ((L - C_v) mod L) N / L) / (N delta_f_RA) seconds late: the fractional window start is put back on
+ * the host.
+ *
+ * float32 arithmetic (restated in tests/prach_oracle.py `detect_f32`): the coherent sum over s in ascending order starting
+ * from Y[..][0]; the product (y.re t.re - y.im t.im, y.re t.im + y.im t.re); the passes of the transforms (the inverse
+ * transform natively: no conjugation) over the radix sequence of the host view with the twiddles W[n] = exp(+j 2 pi n / N),
+ * the last pass scaling by float32(1 / L), computed in double and rounded once; re re + im im per term.  Row q of the
+ * workgroup's rows_per_workgroup rows sums its terms q, q + rows_per_workgroup, .. in ascending order, starting from 0; the rows
+ * are then added in ascending row order.  The sum for mean: thread t < 256 adds P[t], P[t + 256], .. in ascending order, a
+ * butterfly of lane exchanges (distances 32, 16, .., 1) per wave, the four waves as (w0 + w1) + (w2 + w3), times 1 / N
+ * (exact).  An occasion's outputs do not depend on the batch it is in, a root's not on the other roots of the plan.  A NaN or
+ * an infinity in an occasion stays in that occasion; a window that holds no ordered value reports peak NaN and delay 0.
+ *
+ *  y        complex64, row (b, r, s) at b occasion_stride + r port_stride + s rep_stride, strides in complex elements, any
+ *           values >= 0 (a view of the decompressor's grid [slot][port][symbol][subcarrier]; 0 repeats a row); 8-byte
+ *           aligned, read with 8-byte loads.  Only the L elements of each row are read.
+ *  peak     float32 [B][n_roots][n_shifts], delay int32 of the same shape, mean float32 [B][n_roots], and the optional
+ *           profile float32 [B][n_roots][N] (NULL: not written): dense, 4-byte aligned, every element written exactly once.
+ * One launch on `stream`, asynchronous; n_occasions == 0 launches nothing, whatever the pointers.  One 256-thread workgroup
+ * per (occasion, root) loops over the item's terms, rows_per_workgroup at a time; two LDS buffers of N complex64 per row.  No
+ * atomics, no scratch; every address comes from the block index, the thread index and host-derived values.
+ * CE_ERR_INVALID: abi_version != CE_ABI_VERSION; l_ra or n_fft not in the lists, or n_fft <= l_ra; n_roots or n_shifts outside
+ * 1..64; a root outside 1 .. L - 1 or listed twice; n_cs outside 0 .. L - 1; n_shifts n_cs > L; n_cs = 0 with n_shifts > 1;
+ * combine not 0 or 1; a null argument; n_occasions < 0, n_ports outside 1..64, n_reps outside 1..12; a negative stride;
+ * strides whose extent exceeds the address space; y not 8-byte or an output not 4-byte aligned; an output overlapping the
+ * extent (B - 1) occasion_stride + (n_ports - 1) port_stride + (n_reps - 1) rep_stride + L of y.
+ * CE_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups in one launch.
+ */
+typedef struct ce_prach_plan ce_prach_plan; /* opaque */
+
+/* Host only: validation and derivation of ce_prach_plan_create without touching a GPU: the view of the N-point transform,
+ * the n_shifts window starts into `win_start` and the common window length into *win_len. */
+int ce_prach_derive_host(int32_t l_ra, int32_t n_fft, int32_t n_roots, const int32_t* roots, int32_t n_cs, int32_t n_shifts,
+                         int32_t combine, ce_tp_host_view* view, int32_t* win_start, int32_t* win_len);
+
+/* Host only: the plan's tables as (re, im) float32 pairs: the N twiddles W[n] = exp(+j 2 pi n / N) into `twiddles` and the
+ * n_roots x L root table T_i[k] into `table`; either may be NULL and is then left out. */
+int ce_prach_copy_tables(int32_t l_ra, int32_t n_fft, int32_t n_roots, const int32_t* roots, float* twiddles, float* table);
+
+/* Validates the values and uploads the twiddles and the root table to `device`; abi_version = CE_ABI_VERSION. */
+int ce_prach_plan_create(int32_t abi_version, int32_t device, int32_t l_ra, int32_t n_fft, int32_t n_roots, const int32_t* roots,
+                         int32_t n_cs, int32_t n_shifts, int32_t combine, ce_prach_plan** out);
+void ce_prach_plan_destroy(ce_prach_plan* plan);
+
+int ce_prach_detect(const ce_prach_plan* plan, const void* y, int64_t occasion_stride, int64_t port_stride, int64_t rep_stride,
+                    int64_t n_occasions, int32_t n_ports, int32_t n_reps, float* peak, int32_t* delay, float* mean,
+                    float* profile /* may be NULL */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ from .fronthaul import PuschFronthaulCompressor, PuschFronthaulDecompressor, bfp
 from .ldpc import LdpcGraph, PuschLdpcDecoder  # noqa: F401
 from .modulator import PuschModulator  # noqa: F401
 from .ofdm import PuschOfdmDemodulator, PuschOfdmModulator  # noqa: F401
+from .prach import PrachDetector, prach_arrival_seconds, prach_preamble_freq, prach_root_freq, prach_windows  # noqa: F401
 from .precode import PuschTransformPrecoder  # noqa: F401
 from .ratematch import PuschRateRecovery, select_base_graph  # noqa: F401
 from .transportblock import PuschTransportBlock  # noqa: F401

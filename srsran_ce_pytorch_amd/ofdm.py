@@ -17,7 +17,7 @@ the grid's subcarriers onto the bins around DC, the transform, the cyclic prefix
 
 Out of scope: a layer-to-port precoding matrix (identity: one grid row per port), windowing or overlap-add between symbols,
 int16 or fp16 time samples (frequency-domain int16 and block floating point from a 7.2x radio unit: fronthaul.py), a k0 or 7.5 kHz
-shift, PRACH."""
+shift, the time-domain PRACH front end (the detector over frequency-domain rows: prach.py)."""
 from __future__ import annotations
 
 import ctypes as C
