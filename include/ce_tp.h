@@ -6,7 +6,8 @@
  * same host view at the lengths 128 .. 4096, and OFDM modulation, the grid to samples, on the demodulator's plan
  * (ce_ofdmtx_modulate), between those two the time-domain channel emulator (ce_chan_apply), and the other front door, fronthaul
  * I/Q (de)compression between the wire format of an O-RAN 7.2x radio unit and the grid's rows (ce_fh_*), and behind that door
- * PRACH preamble detection over such rows (ce_prach_*), on the same passes.
+ * PRACH preamble detection over such rows (ce_prach_*) and SRS channel estimation over the grid's own rows (ce_srs_*), on the
+ * same passes.
  *
  * The reference (pjookim/srsran-ce-pytorch) stops at the channel estimate.  The operator is pinned by the float64
  * restatement in tests/tp_oracle.py (`deprecode_ref`, against a literal M x M matrix form of 6.3.1.4) and the two
@@ -435,6 +436,114 @@ void ce_prach_plan_destroy(ce_prach_plan* plan);
 int ce_prach_detect(const ce_prach_plan* plan, const void* y, int64_t occasion_stride, int64_t port_stride, int64_t rep_stride,
                     int64_t n_occasions, int32_t n_ports, int32_t n_reps, float* peak, int32_t* delay, float* mean,
                     float* profile /* may be NULL */, void* stream);
+
+/*
+ * SRS CHANNEL ESTIMATION over the frequency-domain grid rows of the sounding reference signal (TS 38.211 6.4.1.4), the third
+ * kind of uplink I/Q in a section-type-1 grid: per item and receive port the power delay profile of the sounding ports
+ * (ce_srs_profile), and, with a delay taken out, the channel per sounding port and 4-PRB block, its wideband mean, the noise
+ * and the received energy (ce_srs_estimate).  Two launches; the delay between them is the caller's (the wrapper's argmax, on
+ * the device).  Scalars and pointers only; the one structure is ce_tp_host_view of the N-point transform (m_sc holds N,
+ * n_workgroups_per_slot is 1: one workgroup per (item, receive port)).
+ *
+ * Plan values:
+ *     k_tc                 2 or 4: the comb.  n_cs_max = 8 (comb 2) or 12 (comb 4)
+ *     n_ap                 1, 2 or 4 sounding ports;  n_cs in 0 .. n_cs_max - 1;  k_bar in 0 .. k_tc - 1
+ *     m_srs                PRBs per symbol, a multiple of 4 in 4 .. 272
+ *     n_symb, l0           1, 2 or 4 consecutive symbols from l0 inside the grid's n_sym <= n_symb_slot (12 or 14) symbols
+ *     start_prb[n_symb]    per symbol, start_prb[s] + m_srs <= n_prb_grid (<= 341).  Frequency hopping is the caller's: the
+ *                          C_SRS / B_SRS table 6.4.1.4.3-1 is the caller's data (host int32, read during the call)
+ *     hopping              CE_DMRS_LP_HOP_NEITHER / _GROUP / _SEQUENCE of ce_dmrs.h;  slots_per_frame 10, 20, 40, 80 or 160
+ *     n_fft = N            128, 256, 512, 1024, 2048 or 4096, N > M
+ *     win_len              1 .. N indices of the profile
+ *     phi                  int8 [30][M] of -3, -1, 1, 3 where M is 12 or 24 (38.211 Tables 5.2.2.2-1/-2: caller data; NULL
+ *                          is CE_ERR_UNSUPPORTED there), ignored otherwise
+ * Derived on the host, in integers: M = 12 m_srs / k_tc sequence elements; a block is 4 PRB = Q = 48 / k_tc elements (a
+ * multiple of n_cs_max: the ports of a comb are exactly orthogonal over a block); n_blocks = m_srs / 4; the guard
+ * g = ceil(N / M); per port i < n_ap
+ *     cs_i = (n_cs + n_cs_max i / n_ap) mod n_cs_max, comb_i = k_bar, except for n_ap = 4 with n_cs >= n_cs_max / 2:
+ *     cs_i = (n_cs + n_cs_max floor(i / 2) / 2) mod n_cs_max, and ports 1 and 3 on comb (k_bar + k_tc / 2) mod k_tc;
+ * the used combs (n_combs = 1 or 2) in the order of their first port.  The default window of the wrapper is
+ * floor(N gap / n_cs_max) - g with gap = n_cs_max / (ports on the fullest comb).
+ *
+ * Sequence: rbar_{u,v}(n), n < M, is the low-PAPR base sequence of 5.2.2 exactly as ce_dmrs_lp_* derive it (ce_dmrs.h): for
+ * M >= 36 W_{N_ZC}[(q[u][v] tri[n]) mod N_ZC] with N_ZC the largest prime below M, for M = 12, 24 exp(j phi_u(n) pi / 4);
+ * M = 30 cannot occur.  Hopping per symbol p = n_symb_slot (slot mod slots_per_frame) + l0 + s: u = (f_gh + n_id) mod 30,
+ * group hopping f_gh = (sum_{m<8} 2^m c(8 p + m)) mod 30, sequence hopping v = c(p) where M >= 72, with c_init = n_id IN
+ * BOTH MODES (6.4.1.4.2; PUSCH's group hopping has floor(n_id / 30)).  Port i transmits rbar(n) rho_i[n],
+ * rho_i[n] = exp(+j 2 pi cs_i n / n_cs_max) (a table of n_cs_max values per port, computed in double and rounded once), on
+ * the subcarriers k(s, comb_i, n) = 12 start_prb[s] + comb_i + k_tc n of symbol l0 + s.
+ *
+ * ce_srs_profile, per item b and receive port r, the TERMS (s, i) in the order s outer, i inner:
+ *     G_i[n]   = y[b][r][l0 + s][k(s, comb_i, n)] conj(rbar(n)) conj(rho_i[n])
+ *     z[d]     = (1 / M) sum_{n<M} G_i[n] exp(+j 2 pi n d / N)
+ *     profile[b][r][d'] = sum over the terms of |z[(d' - g) mod N]|^2,  d' < win_len
+ * A flat unit channel with gains h and no delay puts sum |h|^2 at d' = g.  The delay of an item is
+ * argmax_d' sum_r profile[b][r][d'] - g on the N grid, delay / (N k_tc scs) seconds: torch operations of the wrapper.
+ *
+ * ce_srs_estimate, with d = delay[b] mod N (NULL: 0; any int32, it cannot address memory), the compensation
+ * w[n] = W_N[(n d) mod N] gathered from the plan's twiddles W_N[e] = exp(+j 2 pi e / N), and per used comb c
+ *     g_c[n] = (y[b][r][l0 + s][k(s, c, n)] conj(rbar(n))) w[n]
+ *     h_sb[b][r][i][s][j] = (1 / Q) sum_{n in block j, ascending} g_{comb_i}[n] conj(rho_i[n])
+ *     h_wb[b][r][i]       = the mean of h_sb over (s, j), s outer
+ *     e_c[n]              = g_c[n] - sum_{i: comb_i = c, ascending} h_sb[b][r][i][s][j(n)] rho_i[n]
+ *     noise[b][r]         = sum_{s,c,n} |e_c[n]|^2 / (n_symb n_combs M - n_symb n_ap M / Q)
+ *     epre[b][r]          = the mean of |y|^2 over the same resource elements
+ * The noise comes from the residual itself, never from the difference of two energies.  h_sb is referred to each symbol's
+ * first comb element: the constant phase exp(-j 2 pi (12 start_prb[s] + comb_i) delay / (N k_tc)) of a delayed channel stays
+ * in it (the wrapper's srs_band_response puts it back).
+ *
+ * float32 arithmetic (restated in tests/srs_oracle.py): a conj(b) = (a.re b.re + a.im b.im, a.im b.re - a.re b.im), a b =
+ * (a.re b.re - a.im b.im, a.re b.im + a.im b.re), products in the order written; the passes of the transforms over the view's
+ * radix sequence, the last scaling by float32(1 / M); re re + im im.  Profile: row q of the rows_per_workgroup rows sums its
+ * terms q, q + rows_per_workgroup, .. in ascending order from 0, the rows are added in ascending row order.  Estimate: the
+ * block sum from 0 in ascending n, times float32(1 / Q); the residual subtracts the ports in ascending i; thread t < 256 adds
+ * |e|^2 (and |y|^2) of n = t, t + 256, .. over (s, c) in ascending order, a butterfly of lane exchanges (32, 16, .., 1) per
+ * wave, the four waves as (w0 + w1) + (w2 + w3), times the float32 reciprocal of the count; h_wb from 0 over (s, j), times
+ * float32(1 / (n_symb n_blocks)).  An (item, receive port)'s outputs depend on nothing else: a NaN stays inside its (b, r).
+ *
+ *  y        complex64, row (b, r, symbol) at b item_stride + r port_stride + symbol symbol_stride, strides in complex
+ *           elements, any values >= 0; 8-byte aligned, read with 8-byte loads.  Only the used combs' elements are read.
+ *  slot, n_id, delay   device int32, one per item at the given element stride >= 0 (0: one value for the batch), taken as
+ *           unsigned (slot mod slots_per_frame, n_id mod 30 and the low 31 bits, delay mod N): they cannot address memory
+ *  profile  float32 [B][R][win_len];  h_sb complex64 [B][R][n_ap][n_symb][n_blocks];  h_wb complex64 [B][R][n_ap];  noise,
+ *           epre float32 [B][R]: dense, every element written exactly once
+ * One launch each on `stream`, asynchronous; n_items == 0 launches nothing.  One 256-thread workgroup per (item, receive
+ * port); no atomics, no scratch, nothing read by the host.
+ * CE_ERR_INVALID: abi_version != CE_ABI_VERSION; a plan value outside the ranges above; a null plan or pointer; n_items < 0;
+ * n_rx outside 1..64; a negative stride or an extent beyond the address space; y not 8-byte aligned; slot, n_id, delay, profile,
+ * noise, epre not 4-byte or h_sb, h_wb not 8-byte aligned.  CE_ERR_UNSUPPORTED: M = 12 or 24 without phi; more than 2^31 - 1
+ * workgroups.  Nothing is written on refusal.
+ */
+typedef struct ce_srs_plan ce_srs_plan; /* opaque */
+
+/* Host only: validation and derivation of ce_srs_plan_create without touching a GPU.  Every output may be NULL:
+ * view of the N-point transform; info[10] = M, Q, n_blocks, n_combs, form (CE_DMRS_LP_FORM_*), N_ZC (0: table form), g, the
+ * default win_len, n_words (per row of the hopping table), v_live; port_comb[4], port_cs[4]; q[30][2] and tri[M] (zero in the
+ * table form); hop_words [32][n_words] (row 0: c for c_init = 0, row 1 + i: what bit i of c_init adds). */
+int ce_srs_derive_host(int32_t k_tc, int32_t n_ap, int32_t n_cs, int32_t k_bar, int32_t m_srs, int32_t n_symb, int32_t l0,
+                       const int32_t* start_prb, int32_t n_prb_grid, int32_t n_sym, int32_t n_symb_slot, int32_t hopping,
+                       int32_t slots_per_frame, int32_t n_fft, int32_t win_len, const int8_t* phi, ce_tp_host_view* view,
+                       int32_t* info, int32_t* port_comb, int32_t* port_cs, int32_t* q, int32_t* tri, uint32_t* hop_words);
+
+/* Host only: the plan's tables as (re, im) float32 pairs, each optional (NULL): the N twiddles W_N[e] = exp(+j 2 pi e / N),
+ * the gather table (N_ZC values W[e] = exp(-j 2 pi e / N_ZC), or the four values of the table form) and rho [n_ap][n_cs_max]. */
+int ce_srs_copy_tables(int32_t k_tc, int32_t n_ap, int32_t n_cs, int32_t k_bar, int32_t m_srs, int32_t n_fft, float* twiddles,
+                       float* w_zc, float* rho);
+
+/* Validates the values and uploads the tables to `device`; abi_version = CE_ABI_VERSION. */
+int ce_srs_plan_create(int32_t abi_version, int32_t device, int32_t k_tc, int32_t n_ap, int32_t n_cs, int32_t k_bar, int32_t m_srs,
+                       int32_t n_symb, int32_t l0, const int32_t* start_prb, int32_t n_prb_grid, int32_t n_sym, int32_t n_symb_slot,
+                       int32_t hopping, int32_t slots_per_frame, int32_t n_fft, int32_t win_len, const int8_t* phi, ce_srs_plan** out);
+void ce_srs_plan_destroy(ce_srs_plan* plan);
+
+int ce_srs_profile(const ce_srs_plan* plan, const void* y, int64_t item_stride, int64_t port_stride, int64_t symbol_stride,
+                   int64_t n_items, int32_t n_rx, const int32_t* slot, int64_t slot_stride, const int32_t* n_id, int64_t n_id_stride,
+                   float* profile, void* stream);
+
+int ce_srs_estimate(const ce_srs_plan* plan, const void* y, int64_t item_stride, int64_t port_stride, int64_t symbol_stride,
+                    int64_t n_items, int32_t n_rx, const int32_t* slot, int64_t slot_stride, const int32_t* n_id, int64_t n_id_stride,
+                    const int32_t* delay /* may be NULL */, int64_t delay_stride, void* h_sb, void* h_wb, float* noise, float* epre,
+                    void* stream);
 
 #ifdef __cplusplus
 }

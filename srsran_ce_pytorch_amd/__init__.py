@@ -11,4 +11,5 @@ from .ofdm import PuschOfdmDemodulator, PuschOfdmModulator  # noqa: F401
 from .prach import PrachDetector, prach_arrival_seconds, prach_preamble_freq, prach_root_freq, prach_windows  # noqa: F401
 from .precode import PuschTransformPrecoder  # noqa: F401
 from .ratematch import PuschRateRecovery, select_base_graph  # noqa: F401
+from .srs import SrsEstimate, SrsEstimator, SrsProfile, srs_band_response, srs_map, srs_ports, srs_sequence  # noqa: F401
 from .transportblock import PuschTransportBlock  # noqa: F401

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("CE_HIP_LIB", CSRC / "libce_hip.so"))   # overrid
 KNOBS_LIB_PATH = CSRC / "libce_hip_knobs.so"
 # the estimation kernel template (ce_estimate_kernel.h) is instantiated in slices, one translation unit each, so the
 # units compile concurrently (ce_inst.inc)
-SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_dmrs_lp.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ofdm.hip", "ce_chan.hip", "ce_fh.hip", "ce_prach.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
+SOURCES = ["ce_api.hip", "ce_denoise.hip", "ce_dmrs.hip", "ce_dmrs_lp.hip", "ce_eq.hip", "ce_demod.hip", "ce_rm.hip", "ce_tp.hip", "ce_ofdm.hip", "ce_chan.hip", "ce_fh.hip", "ce_prach.hip", "ce_srs.hip", "ce_ldpc.hip", "ce_tb.hip", "ce_enc.hip", "ce_mod.hip", "ce_inst_reg_h1_f0.hip", "ce_inst_reg_h1_f1.hip", "ce_inst_reg_h1_f1w.hip", "ce_inst_reg_h2_f0.hip",
            "ce_inst_reg_h2_f1.hip", "ce_inst_gen_h1.hip", "ce_inst_gen_h2.hip", "ce_inst_narrow.hip"]
 
 
@@ -284,6 +284,13 @@ REGISTRY["ce_tp.h"] = Header(structs={"ce_tp_desc": TpDesc, "ce_tp_info": TpInfo
     "ce_prach_plan_create": (_int, [_i32, _i32, _i32, _i32, _i32, _P(_i32), _i32, _i32, _i32, _P(_vp)]),
     "ce_prach_plan_destroy": (None, [_vp]),
     "ce_prach_detect": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # SRS channel estimation: scalars and pointers only, the host view is the transforms' (m_sc holds n_fft)
+    "ce_srs_derive_host": (_int, [_i32] * 7 + [_vp] + [_i32] * 7 + [_vp, _P(TpHostView), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ce_srs_copy_tables": (_int, [_i32] * 6 + [_vp, _vp, _vp]),
+    "ce_srs_plan_create": (_int, [_i32] * 9 + [_vp] + [_i32] * 7 + [_vp, _P(_vp)]),
+    "ce_srs_plan_destroy": (None, [_vp]),
+    "ce_srs_profile": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "ce_srs_estimate": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
 })
 CE_FH_NONE, CE_FH_BFP, CE_FH_MAX_PRBS = 0, 1, 341
 CE_LDPC_MAX_ZC, CE_LDPC_MAX_ROWS, CE_LDPC_MAX_COLS, CE_LDPC_MAX_ROW_DEGREE = 384, 46, 68, 19
